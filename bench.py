@@ -8,21 +8,36 @@ bytes) → k_consensus (deep / general tiles), launched back to back on one stre
 parse and H2D are excluded; parse time is reported separately (host_parse_s).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c5] [--shard]
+                    [--dump-outputs DIR] [--full]
 
 Default workload: C5 (chr20 64.4 Mb × 30x, the largest single-GPU config of BASELINE.json;
-its ~0.7 GB batch does not fit the 256 MiB Infinity Cache).  Per-kernel times come from
-HIP events recorded on the launch stream between the stages of every timed step, so each
-kernel's time is a sub-interval of the step it belongs to.
+its ~0.7 GB batch does not fit the 256 MiB Infinity Cache).
 
-N>1 (torch.distributed.run, one process per GPU):
-  default        weak scaling (the path partitions by position: per-GPU work fixed as N
-                 grows): each rank runs its own batch of the workload (seed + rank), as the
-                 position shards of an N-times larger genome would; no collective on the
-                 data path;
-  --shard        strong scaling, the north_star position split of ONE workload: contiguous
+A plain run does only what the headline figure needs: it builds the batch, runs W warmup
+steps, times exactly K steps, writes the last step's outputs if --dump-outputs is given and
+prints the result line (value, ms_per_step, the roofline of the whole step's GPU time).
+--full adds everything else the benchmark measures or checks, each leg with its own
+--no-... switch: the timed SAM-file parse (host_parse_s), the per-stage breakdown (a few
+more steps with HIP events recorded on the launch stream between the stages), the parity
+check against the reference's golden files, the CPU baselines, and with N>1 the weak run
+and the timed exchange.
+
+--dump-outputs DIR: what a caller of the timed path receives after the last timed step
+(Workspace.fetch: statistics, body offsets, FASTA body bytes) as DIR/<name>.npy, float32 /
+float64, under 64 MB in all (dump_outputs; the strong split of N>1: the shards' results
+gathered and merged on rank 0, which runs the exchange for it).  The batch is seeded, so two builds run with the
+same arguments can be compared file for file.
+
+N>1 (torch.distributed.run, one process per GPU; --scaling strong|weak|both, default both):
+  strong         the line's value: the north_star position split of ONE workload: contiguous
                  tile ranges (sam2consensus_amd.shard.split_tiles), each rank runs its shard;
-                 the shards' FASTA bodies and statistics are gathered to rank 0 (RCCL) after
-                 the timed steps and checked against the reference's golden.
+                 --full: the shards' FASTA bodies and statistics are gathered to rank 0 (RCCL)
+                 after the timed steps, the exchange timed, the result checked against the
+                 reference's golden;
+  weak           (--scaling weak, or both with --full: the line's 'weak' record) per-GPU work
+                 fixed as N grows: every rank runs the whole workload on its own GPU, as the
+                 position shards of an N-times larger genome would; no collective on the
+                 data path.
 Timing: barrier + synchronize on both sides of exactly K steps, MAX over ranks; value =
 aligned bases of all ranks / that time.  Rank 0 prints ONE JSON line.
 """
@@ -208,7 +223,7 @@ def spawn_ranks(n, argv):
     return rc
 
 
-def timed_steps(ws, K, W, world, dev, graph=False, stage_events=False):
+def timed_steps(ws, K, W, world, dev, graph=False, stage_events=False, breakdown=True, after_steps=None):
     """W untimed warmup steps, then EXACTLY K steps bracketed by a barrier + synchronize on
     both sides; returns (this rank's seconds, the max over ranks, per-stage GPU ms).
 
@@ -217,7 +232,9 @@ def timed_steps(ws, K, W, world, dev, graph=False, stage_events=False):
     interval / K is the GPU time of a whole step (every stage; C5 launches only the pileup
     kernel), which the roofline prices the pileup's bytes against.  The per-stage split comes
     from a few more steps with events between the stages (--stage-events: events between
-    all stages of every timed step instead)."""
+    all stages of every timed step instead; breakdown=False, a plain run: no such steps).
+    ``after_steps()`` is called once the K steps are done and timed, before any further step
+    (--dump-outputs: the workspace then holds the last timed step's results)."""
     import torch
     import torch.distributed as dist
     stream = torch.cuda.current_stream(dev)
@@ -254,7 +271,9 @@ def timed_steps(ws, K, W, world, dev, graph=False, stage_events=False):
     if world > 1:
         dist.barrier()
     kern = {"step_gpu": span[0].elapsed_time(span[1]) / K}   # ms, the timed steps
-    if not graph:
+    if after_steps is not None:
+        after_steps()
+    if not graph and (stage_events or breakdown):
         if not stage_events:   # the stages from a few more steps with all four events
             ev = [[torch.cuda.Event(enable_timing=True) for _ in range(4)] for _ in range(5)]
             for e in ev:
@@ -283,6 +302,54 @@ def _coll_device(dev):
     return dev if dist.get_backend() == "nccl" else torch.device("cpu")
 
 
+DUMP_SAMPLE = 8 << 20   # body bytes written one by one (float32: 32 MB)
+DUMP_BLOCK = 64         # body bytes per block sum
+DUMP_SEED = 20240611
+
+
+def dump_outputs(outdir, stats, offs, out):
+    """--dump-outputs: the last timed step's results as a caller receives them (Workspace.fetch
+    / shard.gather_device: stats[R,T,4] u64, offs[T·tiles+1] u64, the FASTA body bytes), as
+    .npy files of float32 / float64, under 64 MB in all:
+
+      stats.npy            float64 [R,T,4]   the per-reference statistics (counts < 2^53: exact)
+      offs.npy             float64           the body offsets (at most 2^20 of them: a seeded,
+                                             sorted sample of a longer array, the last included)
+      body_block_sums.npy  float32           the sum of every 64 consecutive body bytes (each
+                                             <= 64·255: exact), so every byte of the output
+                                             counts; for bodies over 256 MB the blocks grow
+      body_sample.npy      float32           the body's bytes: all of them up to 8 Mi, else the
+                                             bytes at 8 Mi seeded, sorted positions
+
+    The sample positions depend only on the array lengths and DUMP_SEED (8 + 16 + 32 MB at most)."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+
+    def pick(n, cap):   # all positions, or a sorted seeded sample that keeps the last one
+        if n <= cap:
+            return np.arange(n, dtype=np.int64)
+        idx = np.unique(rng.integers(0, n, size=cap - 1, dtype=np.int64))
+        return np.union1d(idx, np.array([n - 1], dtype=np.int64))
+
+    np.save(os.path.join(outdir, "stats.npy"), np.asarray(stats).astype(np.float64))
+    offs = np.asarray(offs)
+    np.save(os.path.join(outdir, "offs.npy"), offs[pick(len(offs), 1 << 20)].astype(np.float64))
+    body = np.frombuffer(out, dtype=np.uint8) if isinstance(out, (bytes, bytearray, memoryview)) \
+        else np.asarray(out, dtype=np.uint8).reshape(-1)
+    body = body[: int(offs[-1])] if len(offs) else body[:0]
+    blk = DUMP_BLOCK
+    while len(body) // blk > (4 << 20):   # (at most 4 Mi sums: 16 MB)
+        blk *= 2
+    nfull = len(body) // blk * blk
+    sums = body[:nfull].reshape(-1, blk).sum(axis=1, dtype=np.uint32).astype(np.float32)
+    if nfull < len(body):
+        sums = np.append(sums, np.float32(body[nfull:].sum(dtype=np.uint32)))
+    np.save(os.path.join(outdir, "body_block_sums.npy"), sums)
+    idx = pick(len(body), DUMP_SAMPLE)
+    np.save(os.path.join(outdir, "body_sample.npy"), body[idx].astype(np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -295,12 +362,19 @@ def main():
                          "value = strong, the weak run in the line's 'weak' record")
     ap.add_argument("--shard", action="store_true", help="= --scaling strong")
     ap.add_argument("--independent", action="store_true", help="= --scaling weak")
-    ap.add_argument("--no-file-parse", action="store_true", help="skip the timed SAM-file parse (host_parse_s)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also: the timed SAM-file parse, the per-stage breakdown, the parity check against the "
+                         "golden files, the CPU baselines; N>1: the weak run of --scaling both and the timed "
+                         "exchange (a plain run times the steps and prints the line, nothing else)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's outputs (statistics, body offsets, FASTA body "
+                         "bytes) as DIR/<name>.npy, float32 / float64, under 64 MB in all")
+    ap.add_argument("--no-file-parse", action="store_true", help="--full: skip the timed SAM-file parse (host_parse_s)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
     ap.add_argument("--cpu-sample-scale", type=float, default=0.016)
-    ap.add_argument("--no-cpu-mc", action="store_true", help="skip the multi-threaded C baseline")
+    ap.add_argument("--no-cpu-mc", action="store_true", help="--full: skip the multi-threaded C baseline")
     ap.add_argument("--cpu-mc-scale", type=float, default=1.0)
-    ap.add_argument("--no-parity", action="store_true")
+    ap.add_argument("--no-parity", action="store_true", help="--full: skip the parity check")
     ap.add_argument("--graph", action="store_true", help="time HIP graph replays of the step")
     ap.add_argument("--stage-events", action="store_true", help="HIP events between all stages in the timed steps")
     ap.add_argument("--rehearse-shards", type=int, default=0, metavar="N",
@@ -357,24 +431,30 @@ def main():
     full = configs.synth_batch(wl)   # (every rank the same workload: the seed of the goldens)
     full.workload = wl
     t_synth = time.perf_counter() - t0
+    # a plain run: the timed steps and the line; every other leg rides behind --full
+    do_parity = args.full and not args.no_parity
     file_parse = None
-    if world == 1 and not args.no_file_parse:
+    if world == 1 and args.full and not args.no_file_parse:
         file_parse = time_file_parse(wl, full)
     strong = world == 1 or args.scaling in ("strong", "both")
-    weak = world > 1 and args.scaling in ("weak", "both")
+    weak = world > 1 and (args.scaling == "weak" or (args.scaling == "both" and args.full))
 
     line = None
     if strong:
         # N = 1: the whole workload; N > 1: this rank's contiguous tile range of it
         hb = shard.sub_batch(full, rank, world) if world > 1 else full
         ws = Workspace(DeviceBatch(hb, dev), thresholds, min_depth, b"-")
-        _, elapsed, kern = timed_steps(ws, K, args.warmup, world, dev, args.graph, args.stage_events)
+        dump = (lambda: dump_outputs(args.dump_outputs, *ws.fetch())) if args.dump_outputs and world == 1 else None
+        _, elapsed, kern = timed_steps(ws, K, args.warmup, world, dev, args.graph, args.stage_events, args.full, dump)
         parity, exchange = None, None
         if world > 1:
-            exchange, res = shard_exchange(ws, hb, full, rank, world, T, dev)
-            if not args.no_parity and rank == 0:
-                parity = check_parity_result(wl, full, res, thresholds, world)
-        elif not args.no_parity:
+            if args.full or args.dump_outputs:   # (N > 1: the dump is the merged result on rank 0)
+                exchange, res = shard_exchange(ws, hb, full, rank, world, T, dev)
+                if do_parity and rank == 0:
+                    parity = check_parity_result(wl, full, res, thresholds, world)
+                if args.dump_outputs and rank == 0:
+                    dump_outputs(args.dump_outputs, *res)
+        elif do_parity:
             parity = check_parity(wl, hb, ws, thresholds)
         if rank == 0:
             line = result_line(wl, full, hb, thresholds, K, args, world, backend, elapsed, kern,
@@ -394,8 +474,9 @@ def main():
         # every rank the whole workload on its own GPU: per-GPU work fixed as N grows, no
         # collective on the data path (the position shards of an N-times larger genome)
         ws = Workspace(DeviceBatch(full, dev), thresholds, min_depth, b"-")
-        _, elapsed, kern = timed_steps(ws, K, args.warmup, world, dev, args.graph, args.stage_events)
-        parity = check_parity(wl, full, ws, thresholds) if not args.no_parity and rank == 0 else None
+        dump = (lambda: dump_outputs(args.dump_outputs, *ws.fetch())) if args.dump_outputs and not strong and rank == 0 else None
+        _, elapsed, kern = timed_steps(ws, K, args.warmup, world, dev, args.graph, args.stage_events, args.full, dump)
+        parity = check_parity(wl, full, ws, thresholds) if do_parity and rank == 0 else None
         if rank == 0:
             wline = result_line(wl, full, full, thresholds, K, args, world, backend, elapsed, kern, "weak",
                                 world * full.info.aligned_bases)
@@ -414,7 +495,10 @@ def main():
         if world == 1 and args.rehearse_shards > 1:
             line["shard_rehearsal"] = rehearse_shards(full, args.rehearse_shards, thresholds, min_depth, dev,
                                                       args.steps, args.warmup, full.info.aligned_bases)
-        if world == 1 and not args.no_cpu_baseline:
+        line["full"] = bool(args.full)
+        if args.dump_outputs:
+            line["dump_outputs"] = args.dump_outputs
+        if world == 1 and args.full and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(wl, args.cpu_sample_scale)
             if not args.no_cpu_mc:
                 line["cpu_baseline_mc"] = cpu_baseline_mc(wl, args.cpu_mc_scale)

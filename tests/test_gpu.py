@@ -608,7 +608,7 @@ def test_bench_two_ranks_strong_split_line():
     env = dict(os.environ, S2C_DIST_BACKEND="gloo", OMP_NUM_THREADS="4")
     env.pop("WORLD_SIZE", None)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                        "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=540)
+                        "--full", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=540)
     assert r.returncode == 0, r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -669,3 +669,37 @@ def test_tile_events_and_k_reads_events_agree(tmp_path, ins_frac, ins_max):
         assert sorted(got) == sorted(want), tag
         for fn in want:
             assert got[fn] == want[fn], (tag, fn, _first_diff(got[fn], want[fn]))
+
+
+def test_bench_plain_run_dumps_last_step_outputs(tmp_path):
+    """A plain bench.py run (C1, 3 steps) does the timed steps only — no parity, CPU or parse
+    leg, no breakdown steps — and --dump-outputs writes what Workspace.fetch returns after the
+    last step: the statistics, the offsets and every body byte (C1 is below the sample sizes),
+    equal to the same workload run in this process."""
+    import json
+    import subprocess
+    import sys
+    from sam2consensus_amd import configs
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--workload", "c1", "--dump-outputs", str(out)], capture_output=True, text=True, timeout=240)
+    assert r.returncode == 0, r.stderr[-4000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["value"] > 0 and d["full"] is False
+    assert d["unit"] == "aligned bases/s" and d["higher_is_better"] is True and d["dtype"] == "u32"
+    assert d["parity"] is None and d["host_parse"] is None and "cpu_baseline" not in d
+    assert set(d["kernels_ms"]) == {"step_gpu"}
+    hb = configs.synth_batch("c1")
+    ws = _ws(hb, [0.25])
+    ws.run()
+    stats, offs, body = ws.fetch()
+    body = np.frombuffer(body, dtype=np.uint8)
+    got = {f[:-4]: np.load(str(out / f)) for f in sorted(os.listdir(out))}
+    assert sorted(got) == ["body_block_sums", "body_sample", "offs", "stats"]
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert (got["stats"] == stats.astype(np.float64)).all() and (got["offs"] == offs.astype(np.float64)).all()
+    assert len(body) == int(offs[-1]) and (got["body_sample"] == body.astype(np.float32)).all()
+    assert got["body_block_sums"].sum(dtype=np.float64) == body.sum(dtype=np.float64)

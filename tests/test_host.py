@@ -862,3 +862,33 @@ def test_bench_refuses_world_size_mismatch():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2"], capture_output=True, text=True,
                        env=dict(os.environ, WORLD_SIZE="1", RANK="0", LOCAL_RANK="0"), timeout=60)
     assert r.returncode == 2 and "--gpus 2 but WORLD_SIZE 1" in r.stderr
+
+
+def test_bench_dump_outputs_is_a_fixed_bounded_sample(tmp_path):
+    """bench.py --dump-outputs (dump_outputs): float32 / float64 .npy files; a body and an offset
+    array beyond the sample sizes are sampled at the same positions on every call, the last
+    offset kept, every byte counted in the block sums, and the files stay under 64 MB."""
+    m = _bench_module()
+    rng = np.random.default_rng(5)
+    n = m.DUMP_SAMPLE + 12345
+    body = rng.integers(0, 256, size=n, dtype=np.uint8)
+    offs = np.arange(0, (1 << 20) + 7, dtype=np.uint64) * (n // ((1 << 20) + 6))
+    offs[-1] = n
+    stats = rng.integers(0, 1 << 40, size=(3, 2, 4), dtype=np.uint64)
+    a, b = tmp_path / "a", tmp_path / "b"
+    m.dump_outputs(str(a), stats, offs, memoryview(body.tobytes()))
+    other = body.copy()
+    other[n // 2] ^= 1
+    m.dump_outputs(str(b), stats, offs, memoryview(other.tobytes()))
+    ga = {f: np.load(str(a / f)) for f in os.listdir(a)}
+    gb = {f: np.load(str(b / f)) for f in os.listdir(b)}
+    assert sorted(ga) == ["body_block_sums.npy", "body_sample.npy", "offs.npy", "stats.npy"]
+    assert all(v.dtype in (np.float32, np.float64) for v in ga.values())
+    assert sum(os.path.getsize(str(a / f)) for f in ga) < 64 << 20
+    assert (ga["stats.npy"] == stats.astype(np.float64)).all()
+    assert len(ga["offs.npy"]) <= 1 << 20 and ga["offs.npy"][-1] == n and (np.diff(ga["offs.npy"]) >= 0).all()
+    assert len(ga["body_sample.npy"]) <= m.DUMP_SAMPLE and ga["body_sample.npy"].shape == gb["body_sample.npy"].shape
+    assert ga["body_block_sums.npy"].sum(dtype=np.float64) == body.sum(dtype=np.float64)
+    # one flipped byte shows in exactly one block sum, whether or not the sample holds it
+    assert (ga["body_block_sums.npy"] != gb["body_block_sums.npy"]).sum() == 1
+    assert (ga["body_sample.npy"] != gb["body_sample.npy"]).sum() <= 1
