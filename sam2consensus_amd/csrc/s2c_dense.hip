@@ -8,11 +8,13 @@
 //              range each) — into LDS by buffer LDS-DMA with SGPR offsets (no per-lane address
 //              arithmetic); the lane's piece records into registers.
 //   2. walk    one lane per piece.  The common piece — one M / = / X token, no range, prefix
-//              or long flag — is one run of min(l, len(SEQ)) bases (parsecigar :64-69) and
-//              takes a few instructions; every other piece (D / I / S / H tokens, wrap ranges,
-//              maxdel with '-' chars in SEQ) is queued, and the queue is walked afterwards by
-//              the general parsecigar + maxdel walk (:46-82, :210) with all lanes busy.  Runs
-//              of reads holding N / '-' chars are queued too: their SEQ chars go into the
+//              or long flag, no '-' in SEQ (S2C_PF_SIMPLE) — is one run of `take` bases
+//              (parsecigar :64-69) straight from its record, its one or two 'N' added from the
+//              listed offsets; every other piece is compacted into the wave's queue and handled
+//              afterwards with all lanes busy: the deletion reads (bases, D / N / P, bases) by
+//              two base runs and a '-' range, the rest (I / S / H tokens, wrap ranges, '-' chars
+//              in SEQ) by the general parsecigar + maxdel walk (:46-82, :210).  Runs of reads
+//              holding other N / '-' chars are queued too: their SEQ chars go into the
 //              per-position byte counters in one dense pass.
 //   3. count   the G = 64 / (tile words) lanes of a word count the runs covering it — A C G T
 //              into bit-sliced Harley–Seal counters, 8 records at a time.
@@ -193,7 +195,10 @@ __device__ __forceinline__ uint2 rec_enc_b(uint32_t rs, uint32_t len, uint32_t q
 
 constexpr int WGD = 64;   // one wave per tile
 constexpr int GSD = 8;    // records per counting group (one Harley–Seal tree)
-constexpr int CNT_PART = 2;   // records whose geometry and plane words are in registers at once
+// records whose geometry and plane words are in registers at once (4: 109 VGPRs, the plane
+// reads of four records in flight, no faster on C5 — the SIMD's other waves cover the wait;
+// 8: 129 VGPRs, one wave per SIMD less)
+constexpr int CNT_PART = 2;
 
 // LDS byte address of a shared-memory pointer
 __device__ __forceinline__ uint32_t lds_addr(const void *p) {
@@ -525,148 +530,154 @@ __device__ __forceinline__ void dense_tile(const DenseArgs &d, const Win &v, con
     const uint32_t nitw = (npc + WT - 1) / WT, qcap = WGD * nitw;
     uint32_t *queue = L.q + wv * qcap;
 
-    // ---- walk: one lane per piece → run records {gpos, (query base − 32·qw0) << 15 | len << 4
-    //      | kind} of the bases; the common piece here, the others queued
+    // ---- walk: one lane per piece → run records (rec_enc) of the bases.  The one-token read
+    //      (S2C_PF_SIMPLE, 99 % of C5's pieces) takes the lean path below; every other piece
+    //      is compacted into the wave's queue and walked after the iterations
     const int32_t T0 = (int32_t)(32 * W0), TL = (int32_t)(32 * nwords);   // the tile's words
     const bool mda = d.maxdel_active != 0;
+    // The wave's queue: the other pieces (their window index) from the front, the slots of
+    // runs waiting for the plane scan (X runs) from the back.  Capacity rule: a walk iteration
+    // adds at most one entry per lane (a piece is SIMPLE or not), so after the iterations
+    // nslow + nx ≤ 64·nitw = qcap.  The compacted pass reads a round's front entries before it
+    // writes: while front entries remain for later rounds the back may grow down to entry
+    // nslow (qcap − nslow − nx entries left), in the last round over the whole queue (qcap −
+    // nx); a round whose deletion reads' X runs (≤ 2 entries each) might not fit there sends
+    // those reads through the general walk, which scans their planes itself and queues nothing.
     uint32_t nslow = 0, nx = 0;   // queue lengths (uniform)
     const uint32_t nit = ABL(4) ? 0u : nitw;
-    uint32_t opw[PFN];   // the pieces' first op words, read together
-#pragma unroll
-    for (int u = 0; u < PFN; u++) opw[u] = (tid + WT * u < npc) ? opl[Pc[u].y & 0x1FFFu] : 0u;
-    for (uint32_t it = 0; it < nit; it++) {
-        const uint32_t k = tid + WT * it;
-        uint3 P = Pc[0];
-        uint32_t w0 = opw[0];
-#pragma unroll
-        for (int u = 1; u < PFN; u++) {   // (the loaded records by a select chain)
-            P.x = it == (uint32_t)u ? Pc[u].x : P.x;
-            P.y = it == (uint32_t)u ? Pc[u].y : P.y;
-            P.z = it == (uint32_t)u ? Pc[u].z : P.z;
-            w0 = it == (uint32_t)u ? opw[u] : w0;
-        }
-        const bool in = k < npc;
-        if (it >= (uint32_t)PFN && in) {   // (windows of more than WT·PFN pieces)
-            P = dpc_load(d, v.dpc0 + k);
-            w0 = opl[P.y & 0x1FFFu];
-        }
+    // one M / = / X token and nothing else: seqout = SEQ[0 : take] (:64-69), take in the
+    // record's length field (s2c.h S2C_PF_SIMPLE): no op word read, no min
+    auto lean = [&](uint32_t k, const uint3 P) {
         const DPiece D = dpc_dec(P.x, P.y);
-        const uint32_t pxv = P.z, fl = D.fl, slen = D.slen, j = D.j, nops = D.nops;
-        const uint32_t op = w0 & 15u, l = w0 >> 4;
-        const bool xf = (fl & S2C_PF_X) != 0;
-        // (no maxdel count to take: the rule is off, or SEQ holds no '-'; S2C_PF_SIMPLE marks the
-        // one-token pieces, whose length field already holds take)
-        const bool plain = in && (fl & ~(uint32_t)(S2C_PF_X | S2C_PF_DASH | S2C_PF_SIMPLE | S2C_PF_XFEW)) == 0u && op_bases(op) &&
-                           !((fl & S2C_PF_DASH) && mda);
-        // one M / = / X token and nothing else: seqout = SEQ[0 : min(l, len(SEQ))] (:64-69)
-        const bool fast = plain && nops == 1u;
-        const uint32_t take = min(l, slen), q = D.q;
-        if (fast) runl[j] = rec_enc_b(D.rs, take, q);
-        // bases, D / N / P, bases (the deletion reads): two base runs here (:64-72: k = take,
-        // then l1 '-', then SEQ[l : l + min(l2, len(SEQ) − l)]), the '-' run queued for the byte
-        // counters unless maxdel drops it (:210: l1 dashes); with N / '-' in SEQ (no maxdel
-        // count to take: `plain`) both base runs go to the X-run queue
-        bool fdel = false, fdash = false;
-        uint32_t da = 0, db = 0, t2 = 0, l1 = 0;   // the '-' run's tile-relative range, clipped to the tile
-        if (plain && nops == 3u) {
-            const uint32_t w1 = opl[j + 1], w2 = opl[j + 2];
-            if (op_dash(w1 & 15u) && op_bases(w2 & 15u)) {
-                l1 = w1 >> 4;
-                t2 = l < slen ? min(w2 >> 4, slen - l) : 0u;
-                const int32_t r0 = (int32_t)(D.rs + take) - REC_BIAS;
-                da = (uint32_t)min(max(r0, 0), TL);
-                db = (uint32_t)min(max(r0 + (int32_t)l1, 0), TL);
-                fdel = true;
-                fdash = db > da && !(mda && l1 > d.maxdel);
-                runl[j] = rec_enc_b(D.rs, take, q);
-                runl[j + 1] = make_uint2(0u, 0u);
-                runl[j + 2] = rec_enc_b(D.rs + take + l1, t2, q + l);
-            }
-        }
-        // queue: pieces for the general walk (their index) and the '-' runs of the deletion
-        // reads (1 << 31 | begin << 12 | end, tile-relative: TL ≤ 2048) from the front; the X
-        // runs' slots from the back.  A lane adds ≤ 3 entries (an X deletion read), so while
-        // that could overrun the wave's queue (64 entries kept per walk iteration left) such
-        // reads take the general walk instead (≤ 1 entry per lane)
-        // the 'N' chars of a read whose SEQ holds at most two (S2C_PF_XFEW: their SEQ offsets in
-        // px) straight into the 'N' counters through its runs: SEQ[0 : take) from P.x, the
-        // deletion read's SEQ[l : l + t2) from P.x + take + l1; other reads with non-ACGT chars
-        // queue their runs for the plane scan
-        const bool xfew = (fl & S2C_PF_XFEW) != 0u && (fast || fdel);
-        if (xfew) {
+        const bool in = k < npc, simple = in && (D.fl & S2C_PF_SIMPLE) != 0u;
+        if (simple) {
+            runl[D.j] = rec_enc_b(D.rs, D.slen, D.q);
+            // at most two 'N' in SEQ (S2C_PF_XFEW: their SEQ offsets in px; 0xFFFF = none, never
+            // below take) straight into the 'N' counters
+            if (D.fl & S2C_PF_XFEW) {
 #pragma unroll
-            for (int u = 0; u < 2; u++) {
-                const uint32_t off = (pxv >> (16 * u)) & 0xFFFFu;
-                int32_t r = -1;
-                if (off < take) r = (int32_t)(D.rs + off) - REC_BIAS;
-                else if (fdel && off >= l && off - l < t2) r = (int32_t)(D.rs + take + l1 + (off - l)) - REC_BIAS;
-                if (off != 0xFFFFu && r >= 0 && r < TL) cnt_add1(ncnt, (uint32_t)r);
+                for (int u = 0; u < 2; u++) {
+                    const uint32_t off = (P.z >> (16 * u)) & 0xFFFFu;
+                    const int32_t r = (int32_t)(D.rs + off) - REC_BIAS;
+                    if (off < D.slen && r >= 0 && r < TL) cnt_add1(ncnt, (uint32_t)r);
+                }
             }
         }
-        bool x1 = (fast || fdel) && xf && !xfew, x2 = fdel && xf && !xfew && t2 > 0u;
-        bool qd = (in && !fast && !fdel) || fdash;
-        uint64_t bs = __ballot(qd), bxm = __ballot(x1), bx2 = __ballot(x2);
-        if (nslow + nx + (uint32_t)(__popcll(bs) + __popcll(bxm) + __popcll(bx2)) > qcap - WGD * (nitw - 1u - it)) {
-            if (fdel && xf && !xfew) {
-                fdel = false;
-                fdash = false;
-            }
-            x1 = fast && xf && !xfew;
-            x2 = false;
-            qd = (in && !fast && !fdel) || fdash;
-            bs = __ballot(qd);
-            bxm = __ballot(x1);
-            bx2 = 0;
+        // other non-ACGT chars in SEQ: the run's slot queued for the plane scan
+        const bool x1 = simple && (D.fl & (S2C_PF_X | S2C_PF_XFEW)) == S2C_PF_X;
+        const bool qd = in && !simple;
+        const uint64_t bs = __ballot(qd), bxm = __ballot(x1);
+        if (bs) {
+            if (qd) queue[nslow + mbcnt(bs)] = k;
+            nslow += (uint32_t)__popcll(bs);
         }
-        if (qd) queue[nslow + mbcnt(bs)] = fdel ? 0x80000000u | (da << 12) | db : k;
-        if (x1) queue[qcap - 1u - nx - mbcnt(bxm)] = j;
-        nx += (uint32_t)__popcll(bxm);
-        if (x2) queue[qcap - 1u - nx - mbcnt(bx2)] = j + 2u;
-        nx += (uint32_t)__popcll(bx2);
-        nslow += (uint32_t)__popcll(bs);
+        if (bxm) {
+            if (x1) queue[qcap - 1u - nx - mbcnt(bxm)] = D.j;
+            nx += (uint32_t)__popcll(bxm);
+        }
+    };
+#pragma unroll
+    for (int u = 0; u < PFN; u++)
+        if ((uint32_t)u < nit) lean(tid + WT * u, Pc[u]);
+    for (uint32_t it = PFN; it < nit; it++) {   // (windows of more than WT·PFN pieces)
+        const uint32_t k = tid + WT * it;
+        lean(k, k < npc ? dpc_load(d, v.dpc0 + k) : make_uint3(0u, 0u, 0u));
     }
     // (the queued work below is this wave's own — its queue, its pieces' run records, atomic
     // byte-counter adds — so its LDS writes completing is enough: the other wave's records are
     // needed only by the count, after the barrier that ends the queued walks)
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     PROF_MARK(2);
-    // queued pieces: the general walk; '-' runs and SEQ N / '-' straight into the byte counters.
-    // A queued piece's record comes from the lane that loaded it (ds_bpermute, all lanes on).
+    // queued pieces, one per lane and round.  A piece's record comes from the lane that loaded
+    // it (ds_bpermute, all lanes on).
     for (uint32_t base = 0; base < (ABL(16) ? 0u : nslow); base += WGD) {
         const uint32_t i = base + lane;
-        const uint32_t qe = i < nslow ? queue[i] : 0u;
-        if (i < nslow && (qe >> 31)) cnt_range(dcnt, (int32_t)((qe >> 12) & 0xFFFu), (int32_t)(qe & 0xFFFu), TL);
-        const bool gen = i < nslow && !(qe >> 31);
-        if (!__ballot(gen)) continue;   // (only '-' runs in this round)
-        const uint32_t k = gen ? qe : 0u, it = k / WT;
+        const bool on = i < nslow;
+        const uint32_t k = on ? queue[i] : 0u, it = k / WT;
         const int src = (int)(4 * (k % WGD));   // (k ≡ this wave's lane mod 64: WT is a multiple of 64)
-        uint32_t c0 = 0, c1 = 0;
+        uint32_t c0 = 0, c1 = 0, pxv = 0;
 #pragma unroll
         for (int u = 0; u < PFN; u++) {
             const uint32_t px = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)Pc[u].x);
             const uint32_t py = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)Pc[u].y);
+            const uint32_t pz = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)Pc[u].z);
             const bool me = it == (uint32_t)u;
             c0 = me ? px : c0;
             c1 = me ? py : c1;
+            pxv = me ? pz : pxv;
         }
-        if (gen) {
-            if (it >= (uint32_t)PFN) {   // (windows of more than WT·PFN pieces)
-                const uint3 R = dpc_load(d, v.dpc0 + k);
-                c0 = R.x;
-                c1 = R.y;
+        if (on && it >= (uint32_t)PFN) {   // (windows of more than WT·PFN pieces)
+            const uint3 R = dpc_load(d, v.dpc0 + k);
+            c0 = R.x;
+            c1 = R.y;
+            pxv = R.z;
+        }
+        const DPiece D = dpc_dec(c0, c1);
+        const uint32_t fl = D.fl, slen = D.slen, j = D.j, q = D.q;
+        // bases, D / N / P, bases (the deletion reads) with no maxdel count to take (the rule is
+        // off, or SEQ holds no '-'): two base runs (:64-72: k = take, then l1 '-', then
+        // SEQ[l : l + min(l2, len(SEQ) − l)]) and the '-' run into the byte counters unless
+        // maxdel drops it (:210: l1 dashes)
+        bool fdel = false;
+        uint32_t l = 0, l1 = 0, take = 0, t2 = 0;
+        if (on && D.nops == 3u && (fl & ~(uint32_t)(S2C_PF_X | S2C_PF_DASH | S2C_PF_XFEW)) == 0u && !((fl & S2C_PF_DASH) && mda)) {
+            const uint32_t w0 = opl[j], w1 = opl[j + 1], w2 = opl[j + 2];
+            fdel = op_bases(w0 & 15u) && op_dash(w1 & 15u) && op_bases(w2 & 15u);
+            l = w0 >> 4;
+            l1 = w1 >> 4;
+            take = min(l, slen);
+            t2 = l < slen ? min(w2 >> 4, slen - l) : 0u;
+        }
+        // its non-ACGT chars: ≤ 2 'N' (S2C_PF_XFEW) from px below; else both base runs' slots go
+        // to the X-run queue if they fit (the capacity rule above)
+        const bool xfew = (fl & S2C_PF_XFEW) != 0u;
+        const bool xq = fdel && (fl & S2C_PF_X) != 0u && !xfew;
+        bool x2 = xq && t2 > 0u;
+        uint64_t bx1 = __ballot(xq), bx2 = __ballot(x2);
+        // (front entries [base + 64, nslow) are still to be read: the back stays above nslow
+        // until the last round, which has read every front entry)
+        const uint32_t room = qcap - (base + WGD < nslow ? nslow : 0u);
+        if (bx1 && nx + (uint32_t)(__popcll(bx1) + __popcll(bx2)) > room) {
+            if (xq) fdel = false;
+            x2 = false;
+            bx1 = bx2 = 0;
+        }
+        if (fdel) {
+            runl[j] = rec_enc_b(D.rs, take, q);
+            runl[j + 1] = make_uint2(0u, 0u);
+            runl[j + 2] = rec_enc_b(D.rs + take + l1, t2, q + l);
+            const int32_t r0 = (int32_t)(D.rs + take) - REC_BIAS;
+            if (!(mda && l1 > d.maxdel)) cnt_range(dcnt, r0, r0 + (int32_t)l1, TL);
+            if (xfew) {   // SEQ[0 : take) starts at rs, SEQ[l : l + t2) at rs + take + l1
+#pragma unroll
+                for (int u = 0; u < 2; u++) {
+                    const uint32_t off = (pxv >> (16 * u)) & 0xFFFFu;
+                    int32_t r = -1;
+                    if (off < take) r = (int32_t)(D.rs + off) - REC_BIAS;
+                    else if (off >= l && off - l < t2) r = (int32_t)(D.rs + take + l1 + (off - l)) - REC_BIAS;
+                    if (off != 0xFFFFu && r >= 0 && r < TL) cnt_add1(ncnt, (uint32_t)r);
+                }
             }
-            const DPiece D = dpc_dec(c0, c1);
+        }
+        if (bx1) {
+            if (xq) queue[qcap - 1u - nx - mbcnt(bx1)] = j;
+            nx += (uint32_t)__popcll(bx1);
+            if (x2) queue[qcap - 1u - nx - mbcnt(bx2)] = j + 2u;
+            nx += (uint32_t)__popcll(bx2);
+        }
+        // the rest: the general walk; '-' runs and SEQ N / '-' straight into the byte counters
+        if (on && !fdel) {
             // (walk_window's view: the global start position and len(SEQ) | flags << 24)
-            const uint4 P = make_uint4((uint32_t)T0 + D.rs - (uint32_t)REC_BIAS, 0u, 0u, D.slen | D.fl << 24);
-            const bool lng = (D.fl & S2C_PF_LONG) != 0;   // (a long piece starting here does not overlap the tile)
-            walk_window(opl, bql, bxl, P, D.j, D.j + D.nops, D.q, mda, d.maxdel,
-                        [&](uint32_t j, uint32_t gp, uint32_t l, uint32_t kind, uint32_t q) {
+            const uint4 P = make_uint4((uint32_t)T0 + D.rs - (uint32_t)REC_BIAS, 0u, 0u, slen | fl << 24);
+            const bool lng = (fl & S2C_PF_LONG) != 0;   // (a long piece starting here does not overlap the tile)
+            walk_window(opl, bql, bxl, P, j, j + D.nops, q, mda, d.maxdel,
+                        [&](uint32_t jr, uint32_t gp, uint32_t rl, uint32_t kind, uint32_t rq) {
                             const uint32_t kd = (lng || kind == S2C_RUN_EMPTY) ? 0u : (kind & 3u);
-                            runl[j] = kd == S2C_RUN_BASES ? rec_enc(gp - (uint32_t)T0, l, q) : make_uint2(0u, 0u);
+                            runl[jr] = kd == S2C_RUN_BASES ? rec_enc(gp - (uint32_t)T0, rl, rq) : make_uint2(0u, 0u);
                             const int32_t r0 = (int32_t)gp - T0;
-                            if (kd == S2C_RUN_DASH) cnt_range(dcnt, r0, r0 + (int32_t)l, TL);
+                            if (kd == S2C_RUN_DASH) cnt_range(dcnt, r0, r0 + (int32_t)rl, TL);
                             if (kd == S2C_RUN_BASES && (kind & S2C_RUN_XBIT))
-                                x_events(bxl, bql, q, l, r0, TL, (kind & S2C_RUN_DROP) != 0, dcnt, ncnt, ccnt);
+                                x_events(bxl, bql, rq, rl, r0, TL, (kind & S2C_RUN_DROP) != 0, dcnt, ncnt, ccnt);
                         });
         }
     }
