@@ -525,6 +525,23 @@ int s2c_run(const s2c_dev *d, void *stream);
 int s2c_gather_bodies_dev(const uint8_t *out, int64_t out_len, const int64_t *starts, const int64_t *offs,
                           int64_t n, uint8_t *dst, void *stream);
 
+/* Per-position count tables as text (the CLI's --counts; csrc/s2c_table.hip).  One line per
+ * position, "P\tCOV\tn-\tnA\tnC\tnG\tnN\tnT\n": COV the sum of the six counts (64-bit), the
+ * counts in S2C_NSYM order, plain decimal.  counts = any device [6][padded_len] u32 array laid
+ * out as s2c_dev.counts; blocks = device [n][3] int64 {a, b, p0}: global positions [a, b) with
+ * 0 <= a <= b <= padded_len, p0 the number printed for position a (0 <= p0, every printed
+ * position below 10^10, so a line is at most 89 bytes).  Two passes: s2c_table_len writes
+ * lens[i], the exact bytes of block i's text (0 for a block outside those bounds); the caller
+ * forms offs[n + 1], the exclusive prefix sum (device int64); s2c_table_write then writes
+ * block i to dst[offs[i], offs[i+1]) and no byte outside it.  A block outside the bounds
+ * above, or with offs[i] < 0, offs[i+1] < offs[i] or offs[i+1] > dst_len, is skipped.  Both
+ * calls are asynchronous on stream and allocate nothing; they add no struct field (ABI 14
+ * stands). */
+int s2c_table_len(const uint32_t *counts, int64_t padded_len, const int64_t *blocks, int64_t n,
+                  int64_t *lens, void *stream);
+int s2c_table_write(const uint32_t *counts, int64_t padded_len, const int64_t *blocks, const int64_t *offs,
+                    int64_t n, uint8_t *dst, int64_t dst_len, void *stream);
+
 /* Diagnostics (tests only, not part of the product path): k_reads over every piece, then
  * every tile's counts stored to d->counts ([6][padded_len] u32) and no vote. */
 int s2c_pileup_counts(const s2c_dev *d, void *stream);

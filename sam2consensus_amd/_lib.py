@@ -119,7 +119,7 @@ EXPORTS = [
     "s2c_batch_layers", "s2c_batch_layers_mode", "s2c_batch_info_get", "s2c_batch_arrays_get", "s2c_batch_ref_name", "s2c_batch_free", "s2c_batch_shard",
     "s2c_parsecigar", "s2c_synth_feed", "s2c_synth_write",
     "s2c_workspace_sizes", "s2c_reads", "s2c_pileup", "s2c_consensus", "s2c_run", "s2c_pileup_counts",
-    "s2c_gather_bodies_dev", "s2c_plan_set_cus",
+    "s2c_gather_bodies_dev", "s2c_plan_set_cus", "s2c_table_len", "s2c_table_write",
 ]
 
 
@@ -197,6 +197,8 @@ def _load():
         "s2c_run": (C.c_int, [C.POINTER(Dev), _VP]),
         "s2c_gather_bodies_dev": (C.c_int, [_VP, C.c_int64, _VP, _VP, C.c_int64, _VP, _VP]),
         "s2c_plan_set_cus": (C.c_int, [C.c_int64]),
+        "s2c_table_len": (C.c_int, [_VP, C.c_int64, _VP, C.c_int64, _VP, _VP]),
+        "s2c_table_write": (C.c_int, [_VP, C.c_int64, _VP, _VP, C.c_int64, _VP, C.c_int64, _VP]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)

@@ -45,6 +45,11 @@ def build_parser():
     # as greater than every int, so the maxdel filter (:210) is then never applied.
     p.add_argument("-d", "--maxdel", action="store", dest="maxdel", default=150,
                    help="Ignore deletions longer than this value, default=150")
+    p.add_argument("--counts", action="store_true", dest="counts", default=False,
+                   help="Also write REF__PREFIX.counts.tsv beside each FASTA file: one line per reference position "
+                        "with the position, the coverage and the counts of -, A, C, G, N, T (tab-separated; "
+                        "insertion columns are not part of the table; independent of -c, -m, -f and -n). "
+                        "Not available with more than one process or with S2C_STREAM")
     return p
 
 
@@ -63,18 +68,21 @@ class RunResult:
         return self
 
 
-def consensus_batch(hb, thresholds, prefix, min_depth=1, fill=b"-", nchar=0, device=None, timings=None):
-    """Device pipeline on a parsed HostBatch → {``REF__PREFIX.fasta``: bytes}."""
+def consensus_batch(hb, thresholds, prefix, min_depth=1, fill=b"-", nchar=0, device=None, timings=None,
+                    counts=False):
+    """Device pipeline on a parsed HostBatch → {``REF__PREFIX.fasta``: bytes}; with ``counts``
+    also the ``REF__PREFIX.counts.tsv`` count tables (table.py), after the FASTA entries — the
+    run then takes the counts route (``Workspace.run_with_counts``)."""
     import torch
 
-    from .engine import _UPLOADERS, DeviceBatch, Workspace, needs_dense_layers
+    from .engine import _UPLOADERS, DeviceBatch, Workspace, needs_dense_layers, to_host
     from .records import build_records, render
 
     t = timings if timings is not None else {}
     t0 = time.perf_counter()
-    db = DeviceBatch(hb, device, dense_layers=needs_dense_layers(fill))
+    db = DeviceBatch(hb, device, dense_layers=needs_dense_layers(fill, counts))
     t1 = time.perf_counter()
-    ws = Workspace(db, thresholds, min_depth, fill)
+    ws = Workspace(db, thresholds, min_depth, fill, keep_counts=bool(counts))
     torch.cuda.synchronize(db.device)
     t["h2d"] = time.perf_counter() - t0
     t["h2d_issue"] = t1 - t0   # (layers + pinned staging + copies issued; the rest: workspace + drain)
@@ -82,7 +90,10 @@ def consensus_batch(hb, thresholds, prefix, min_depth=1, fill=b"-", nchar=0, dev
     if up is not None:   # (the pinned ring's cumulative host seconds: alloc, wait, pack, issue)
         t.update(("h2d_up_" + k, v) for k, v in up.timing.items())
     t0 = time.perf_counter()
-    ws.run()
+    if counts:
+        toffs, ttext = ws.run_with_counts()
+    else:
+        ws.run()
     torch.cuda.synchronize(db.device)
     t1 = time.perf_counter()
     stats, offs, out = ws.fetch()
@@ -94,6 +105,9 @@ def consensus_batch(hb, thresholds, prefix, min_depth=1, fill=b"-", nchar=0, dev
     files = {}
     for name, recs in fastas.items():
         files[name.encode("latin-1") + b"__" + pre + b".fasta"] = render(recs, nchar)
+    if counts:   # (after build_records: a vote error raises and no file is returned)
+        from .table import table_files
+        files.update(table_files(hb, pre, toffs, to_host(ttext)))
     t["format"] = time.perf_counter() - t0
     return files
 
@@ -203,11 +217,45 @@ def consensus_batch_hip(sess, hb, thresholds, prefix, min_depth=1, fill=b"-", nc
     return files
 
 
+def _consensus_files_counts(filename, thresholds, prefix, min_depth, fill, nchar, maxdel_active, device, log):
+    """consensus_files with the count tables: the torch engine path (consensus_batch)."""
+    import torch
+
+    from . import _lib
+    from .batch import Parser
+
+    t = {}
+    t0 = time.perf_counter()
+    dev = torch.device(device if device is not None else "cuda:%d" % int(os.environ.get("LOCAL_RANK", "0")))
+    if dev.type != "cuda" or not torch.cuda.is_available():
+        raise RuntimeError("sam2consensus_amd needs a ROCm GPU (torch.cuda unavailable); no CPU fallback")
+    _lib.plan_for_device(dev)   # (the plan's grid shaping, before the parse builds it)
+    p = Parser(maxdel_active, 150)
+    try:
+        p.feed_file(filename)
+        hb = p.finish()
+    except REF_ERRORS:
+        if log:
+            _log_failed_parse(log, p)
+        raise
+    finally:
+        p.close()
+    t["parse"] = time.perf_counter() - t0
+    if log:
+        _log_summary(log, hb.info)
+    files = consensus_batch(hb, thresholds, prefix, min_depth, fill, nchar, dev, t, counts=True)
+    return RunResult(files, t, hb.info, hb.free_async())
+
+
 def consensus_files(filename, thresholds, prefix, min_depth=1, fill=b"-", nchar=0, maxdel_active=True,
-                    device=None, log=None):
+                    device=None, log=None, counts=False):
     """Run the whole pipeline on one SAM/SAM.gz file; returns a RunResult whose
     ``files`` maps ``REF__PREFIX.fasta`` → content bytes (nothing written).  The device side
-    runs through the HIP runtime directly (hiprun.py): this path never imports PyTorch."""
+    runs through the HIP runtime directly (hiprun.py): this path never imports PyTorch.
+    With ``counts`` the files also hold the ``REF__PREFIX.counts.tsv`` count tables, and the
+    run goes through the torch engine path instead (``consensus_batch(counts=True)``)."""
+    if counts:
+        return _consensus_files_counts(filename, thresholds, prefix, min_depth, fill, nchar, maxdel_active, device, log)
     from .batch import Parser
     from .hiprun import Session, device_index
 
@@ -239,9 +287,10 @@ def consensus_files(filename, thresholds, prefix, min_depth=1, fill=b"-", nchar=
     return RunResult(files, t, hb.info, hb.free_async())
 
 
-def run_text(sam_text, argv, device=None):
+def run_text(sam_text, argv, device=None, counts=False):
     """Library entry for tests: SAM text + CLI args (without -i) → (status, {fname: str}).
-    status is "ok" or the reference's exception class name; nothing touches the disk."""
+    status is "ok" or the reference's exception class name; nothing touches the disk.
+    ``counts`` (or ``--counts`` among the args): the count tables too."""
     from .batch import parse_text
 
     args = build_parser().parse_args(["-i", "in.sam"] + list(argv))
@@ -250,7 +299,7 @@ def run_text(sam_text, argv, device=None):
         prefix = args.prefix or "in"
         hb = parse_text(sam_text, not isinstance(args.maxdel, str), 150)
         files = consensus_batch(hb, thresholds, os.fsencode(prefix), args.min_depth,
-                                os.fsencode(args.fill), args.n, device)
+                                os.fsencode(args.fill), args.n, device, counts=bool(counts or args.counts))
     except (KeyError, IndexError, ValueError, ZeroDivisionError, OverflowError) as e:
         return type(e).__name__, {}
     return "ok", {k.decode("latin-1"): v.decode("latin-1") for k, v in files.items()}
@@ -317,7 +366,13 @@ def consensus_files_sharded(filename, thresholds, prefix, min_depth, fill, nchar
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    if args.counts:   # (refused before a folder is made or a device touched)
+        if _dist_env()[0] > 1:
+            parser.error("--counts is not available with more than one process (WORLD_SIZE > 1)")
+        if os.environ.get("S2C_STREAM"):
+            parser.error("--counts is not available with streamed batches (S2C_STREAM)")
     filename = args.filename
     thresholds = [float(i) for i in args.thresholds.split(",")]                # :117-118
     if args.prefix == "":
@@ -347,19 +402,25 @@ def main(argv=None):
                                              batch_bytes=sb).files
         else:
             res = consensus_files(filename, thresholds, os.fsencode(prefix), args.min_depth,
-                                  os.fsencode(args.fill), args.n, maxdel_active, log=lambda s: print(s))
+                                  os.fsencode(args.fill), args.n, maxdel_active, log=lambda s: print(s),
+                                  counts=args.counts)
             files = res.files
+    tables = []
     for fname, body in files.items():                                             # :411-424
         path = os.fsencode(outfolder) + fname
         with open(path, "wb") as fh:
             fh.write(body)
         shown = os.fsdecode(path)
-        if len(thresholds) == 1:
+        if args.counts and fname.endswith(b".counts.tsv"):
+            tables.append("Count table saved for " + os.fsdecode(fname[: fname.rfind(b"__")]) + " in: " + shown)
+        elif len(thresholds) == 1:
             print("Consensus sequence at " + str(int(thresholds[0] * 100)) + "% saved for " +
                   os.fsdecode(fname[: fname.rfind(b"__")]) + " in: " + shown)
         else:
             print("Consensus sequences at " + ",".join([str(int(i * 100)) + "%" for i in thresholds]) +
                   " saved for " + os.fsdecode(fname[: fname.rfind(b"__")]) + " in: " + shown)
+    for line in tables:
+        print(line)
     if res is not None:
         res.wait()
     print("Done.\n")

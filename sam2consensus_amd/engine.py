@@ -350,6 +350,65 @@ class Workspace:
         d.deep, d.n_deep = _ptr(self._all_tiles), nt
         L.check(lib.s2c_consensus(C.byref(d), self.stream_handle()))
 
+    def _table_blocks(self):
+        """Device int64 [n_tiles][3] {a, b, p0}: one block of the count table per tile (tiles
+        never straddle a reference), p0 = a - ref_off[ref] + 1 the 1-based position of its
+        first row; the tiles of a reference without coverage are empty blocks (no table is
+        written for it, :334-341)."""
+        if getattr(self, "_tblocks", None) is None:
+            hb = self.db.hb
+            tl = hb.tiles[:, :3].astype(np.int64)
+            blocks = np.empty((len(tl), 3), dtype=np.int64)
+            blocks[:, 0] = tl[:, 0]
+            blocks[:, 1] = np.where(hb.ref_reads[tl[:, 2]] > 0, tl[:, 1], tl[:, 0])
+            blocks[:, 2] = tl[:, 0] - hb.ref_off[tl[:, 2]] + 1
+            self._tblocks = _up(blocks.reshape(-1), self.db.device)
+        return self._tblocks
+
+    def counts_table(self):
+        """The filled ``counts`` as the text of the count tables (table.py; s2c_table_len, the
+        prefix sum, s2c_table_write on the current stream): (offs[n_tiles + 1] int64 numpy,
+        device uint8 tensor of exactly offs[-1] bytes) — tile k's rows at [offs[k], offs[k+1]),
+        a reference's table its tiles' rows in order.  Needs keep_counts=True (every tile's
+        counts in HBM) and counts a counts-only stage has filled."""
+        if not self.keep_counts or self.tile_range is not None:
+            raise ValueError("counts_table needs Workspace(keep_counts=True) over the whole batch")
+        if not self._counts_filled:
+            raise ValueError("counts_table needs filled counts (accumulate / pileup_counts; s2c_consensus zeroes them)")
+        i = self.db.info
+        dev = self.db.device
+        nt = int(i.n_tiles)
+        if nt == 0:
+            return np.zeros(1, dtype=np.int64), torch.empty(0, dtype=torch.uint8, device=dev)
+        st = self.stream_handle()
+        blocks = self._table_blocks()
+        offs_d = torch.zeros(nt + 1, dtype=torch.int64, device=dev)
+        lens = torch.empty(nt, dtype=torch.int64, device=dev)
+        L.check(lib.s2c_table_len(_ptr(self.counts), i.padded_len, _ptr(blocks), nt, _ptr(lens), st))
+        torch.cumsum(lens, 0, out=offs_d[1:])
+        offs = offs_d.cpu().numpy()
+        total = int(offs[-1])
+        text = torch.empty(max(total, 16), dtype=torch.uint8, device=dev)
+        L.check(lib.s2c_table_write(_ptr(self.counts), i.padded_len, _ptr(blocks), _ptr(offs_d), nt, _ptr(text),
+                                    total, st))
+        return offs, text[:total]
+
+    def run_with_counts(self):
+        """``run()`` through the counts route, with the count tables: every tile's counts
+        stored (s2c_accumulate on zeroed counts, the insertion tables kept), formatted as text
+        (``counts_table`` — before the vote, which leaves the counts zero), then every tile
+        voted from them (``vote_all``); ``fetch()`` yields the FASTA results as after
+        ``run()``.  Returns counts_table()'s (offs, device text)."""
+        if not self.keep_counts:
+            raise ValueError("run_with_counts needs Workspace(keep_counts=True)")
+        self._counts_ready()
+        # (set first: if a stage raises, a reused workspace zeroes its counts before its next run)
+        self._counts_filled = True
+        self.accumulate(keep_tables=True)
+        table = self.counts_table()
+        self.vote_all()
+        return table
+
     def pileup_counts(self):
         """Diagnostic: k_reads, then every tile's counts stored to `counts` (no vote); needs
         keep_counts=True; returns counts[6][padded_len] as numpy u32."""
