@@ -9,13 +9,17 @@ BUILD    = build
 CXXFLAGS = -O3 -std=c++17 -fPIC -pthread -Wall -Wextra -Iinclude
 HIPFLAGS = -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -ffp-contract=off -Iinclude \
            -Wno-unused-result
+LINK     = $(HIPCC) -shared -fPIC --offload-arch=$(ARCH) $^ -lz -lpthread -o $@
+
+# the one list of host sources (every csrc/*.cpp) and of kernel sources
+HOSTSRC  = $(wildcard $(SRC)/*.cpp)
+HOSTOBJ  = $(HOSTSRC:$(SRC)/%.cpp=$(BUILD)/%.o)
+KERNELS  = s2c_reads s2c_tile s2c_dense s2c_bodies s2c_table
+KOBJ     = $(KERNELS:%=$(BUILD)/%.o)
 
 all: $(OUT)
 
-$(BUILD)/s2c_host.o: $(SRC)/s2c_host.cpp include/s2c.h | $(BUILD)
-	$(CXX) $(CXXFLAGS) -c $< -o $@
-
-$(BUILD)/s2c_synth.o: $(SRC)/s2c_synth.cpp include/s2c.h | $(BUILD)
+$(BUILD)/%.o: $(SRC)/%.cpp $(SRC)/s2c_host_internal.h include/s2c.h | $(BUILD)
 	$(CXX) $(CXXFLAGS) -c $< -o $@
 
 # (every kernel's resource remarks checked: a spill fails the build, scripts/check_spills.py)
@@ -23,22 +27,37 @@ $(BUILD)/%.o: $(SRC)/%.hip $(SRC)/s2c_common.h include/s2c.h scripts/check_spill
 	$(HIPCC) $(HIPFLAGS) -Rpass-analysis=kernel-resource-usage -c $< -o $@ 2> $(BUILD)/$*.usage || { cat $(BUILD)/$*.usage; exit 1; }
 	python3 scripts/check_spills.py $(BUILD)/$*.usage || { rm -f $@; exit 1; }
 
-KOBJ = $(BUILD)/s2c_reads.o $(BUILD)/s2c_tile.o $(BUILD)/s2c_dense.o $(BUILD)/s2c_bodies.o \
-       $(BUILD)/s2c_table.o
-
-$(OUT): $(BUILD)/s2c_host.o $(BUILD)/s2c_synth.o $(KOBJ)
-	$(HIPCC) -shared -fPIC --offload-arch=$(ARCH) $^ -lz -lpthread -o $@
+$(OUT): $(HOSTOBJ) $(KOBJ)
+	$(LINK)
 
 $(BUILD):
 	mkdir -p $(BUILD)
 
-# diagnostic build: phase clocks of k_tile_dense (S2C_LIB=libs2c_prof.so, scripts/prof_dense.py)
-PROF_OUT = sam2consensus_amd/libs2c_prof.so
-prof: $(BUILD)/s2c_host.o $(BUILD)/s2c_synth.o $(BUILD)/s2c_reads.o $(BUILD)/s2c_bodies.o $(BUILD)/s2c_table.o $(SRC)/s2c_tile.hip $(SRC)/s2c_dense.hip $(SRC)/s2c_common.h
-	$(HIPCC) $(HIPFLAGS) $(VDEFS) -DS2C_PROF -c $(SRC)/s2c_dense.hip -o $(BUILD)/s2c_dense_prof.o
-	$(HIPCC) $(HIPFLAGS) $(VDEFS) -DS2C_PROF -c $(SRC)/s2c_tile.hip -o $(BUILD)/s2c_tile_prof.o
-	$(HIPCC) -shared -fPIC --offload-arch=$(ARCH) $(BUILD)/s2c_host.o $(BUILD)/s2c_synth.o $(BUILD)/s2c_reads.o $(BUILD)/s2c_bodies.o $(BUILD)/s2c_table.o \
-	  $(BUILD)/s2c_tile_prof.o $(BUILD)/s2c_dense_prof.o -lz -lpthread -o $(PROF_OUT)
+# Diagnostic and experiment builds: libs2c_<suffix>.so = the host objects, the kernels named in
+# DIAG_<suffix> rebuilt with DEFS_<suffix> (objects build/<kernel>_<suffix>.o), the others as built.
+#   prof      phase clocks of k_tile_dense (S2C_LIB=libs2c_prof.so, scripts/prof_dense.py)
+#   poison    every kernel fills its workgroup's LDS with 0xA5 at entry (S2C_LIB=libs2c_poison.so;
+#             the GPU suite once under it shows no kernel reads LDS it did not write in that launch)
+#   variant   k_reads, k_tile_dense and k_tile with extra defines (V=name VDEFS='-D...'): libs2c_$(V).so
+V     ?= var
+VDEFS ?=
+DIAG_prof   = s2c_dense s2c_tile
+DEFS_prof   = $(VDEFS) -DS2C_PROF
+DIAG_poison = $(KERNELS)
+DEFS_poison = -DS2C_LDS_POISON
+DIAG_$(V)   = s2c_reads s2c_dense s2c_tile
+DEFS_$(V)   = $(VDEFS)
+prof: sam2consensus_amd/libs2c_prof.so
+poison: sam2consensus_amd/libs2c_poison.so
+variant: sam2consensus_amd/libs2c_$(V).so
+
+define DIAG_RULES
+$$(BUILD)/%_$(1).o: $$(SRC)/%.hip $$(SRC)/s2c_common.h include/s2c.h FORCE | $$(BUILD)
+	$$(HIPCC) $$(HIPFLAGS) $$(DEFS_$(1)) -c $$< -o $$@
+sam2consensus_amd/libs2c_$(1).so: $$(HOSTOBJ) $$(filter-out $$(DIAG_$(1):%=$$(BUILD)/%.o),$$(KOBJ)) $$(DIAG_$(1):%=$$(BUILD)/%_$(1).o)
+	$$(LINK)
+endef
+$(foreach s,$(sort prof poison $(V)),$(eval $(call DIAG_RULES,$(s))))
 
 # kernel resource usage (VGPR/SGPR/LDS/occupancy) and ISA for inspection
 ISA_DIR ?= /tmp/s2c_isa
@@ -51,24 +70,5 @@ isa:
 clean:
 	rm -rf $(BUILD) $(OUT)
 
-# diagnostic build: every kernel fills its workgroup's LDS with 0xA5 at entry (S2C_LIB=libs2c_poison.so;
-# the GPU suite once under it shows no kernel reads LDS it did not write in that launch)
-poison: $(BUILD)/s2c_host.o $(BUILD)/s2c_synth.o
-	$(HIPCC) $(HIPFLAGS) -DS2C_LDS_POISON -c $(SRC)/s2c_reads.hip -o $(BUILD)/s2c_reads_poison.o
-	$(HIPCC) $(HIPFLAGS) -DS2C_LDS_POISON -c $(SRC)/s2c_dense.hip -o $(BUILD)/s2c_dense_poison.o
-	$(HIPCC) $(HIPFLAGS) -DS2C_LDS_POISON -c $(SRC)/s2c_tile.hip -o $(BUILD)/s2c_tile_poison.o
-	$(HIPCC) $(HIPFLAGS) -DS2C_LDS_POISON -c $(SRC)/s2c_bodies.hip -o $(BUILD)/s2c_bodies_poison.o
-	$(HIPCC) $(HIPFLAGS) -DS2C_LDS_POISON -c $(SRC)/s2c_table.hip -o $(BUILD)/s2c_table_poison.o
-	$(HIPCC) -shared -fPIC --offload-arch=$(ARCH) $^ $(BUILD)/s2c_reads_poison.o $(BUILD)/s2c_dense_poison.o \
-	  $(BUILD)/s2c_tile_poison.o $(BUILD)/s2c_bodies_poison.o $(BUILD)/s2c_table_poison.o -lz -lpthread -o sam2consensus_amd/libs2c_poison.so
-
-.PHONY: all clean isa prof variant poison
-
-# experiment build: k_reads, k_tile_dense and k_tile with extra defines (V=name VDEFS='-D...'): libs2c_$(V).so
-V ?= var
-VDEFS ?=
-variant: $(BUILD)/s2c_host.o $(BUILD)/s2c_synth.o $(BUILD)/s2c_bodies.o $(BUILD)/s2c_table.o
-	$(HIPCC) $(HIPFLAGS) $(VDEFS) -c $(SRC)/s2c_reads.hip -o $(BUILD)/s2c_reads_$(V).o
-	$(HIPCC) $(HIPFLAGS) $(VDEFS) -c $(SRC)/s2c_dense.hip -o $(BUILD)/s2c_dense_$(V).o
-	$(HIPCC) $(HIPFLAGS) $(VDEFS) -c $(SRC)/s2c_tile.hip -o $(BUILD)/s2c_tile_$(V).o
-	$(HIPCC) -shared -fPIC --offload-arch=$(ARCH) $^ $(BUILD)/s2c_reads_$(V).o $(BUILD)/s2c_dense_$(V).o $(BUILD)/s2c_tile_$(V).o -lz -lpthread -o sam2consensus_amd/libs2c_$(V).so
+FORCE:   # (a diagnostic object is rebuilt every time: its defines come from the command line)
+.PHONY: all clean isa prof variant poison FORCE

@@ -1,7 +1,7 @@
 """Host side of the packed read batch (north_star subsystem 1).
 
 ``parse_file`` / ``parse_text`` / ``synth_batch`` drive libs2c.so's parser
-(s2c_host.cpp), which reproduces the reference's read pass
+(s2c_parse.cpp, s2c_plan.cpp), which reproduces the reference's read pass
 (sam2consensus.py:147-228) and reformat-phase checks (:284-294), and returns a
 ``HostBatch`` whose arrays are zero-copy numpy views of the C++ buffers.
 """

@@ -1,7 +1,7 @@
 // s2c_reads.hip — k_reads: the reference's parsecigar (:46-82), maxdel rule (:210) and
 // insertion collection (:73-75, :221, :262-271) on the device, one thread per piece.
 //
-// Input: the packed batch of s2c_host.cpp — per piece its global start, its read's CIGAR
+// Input: the packed batch of s2c_plan.cpp — per piece its global start, its read's CIGAR
 // tokens (:58 regex matches) and SEQ as query-order base planes.  The thread walks the
 // tokens exactly as parsecigar does (start = query index, k = seqout index):
 //   M / = / X   take = min(l, len(SEQ) - start) bases (SEQ truncation, :67), k += take

@@ -6,35 +6,9 @@
 // Everything is derived from splitmix64 streams keyed by (seed, read index), so the
 // bytes are identical on every machine; the same generator feeds the golden run of the
 // reference (oracle/gen_golden_configs.py), the CLI tests and bench.py.
-#include <thread>
-#include "../../include/s2c.h"
-
-#include <new>
-#include <stdexcept>
-#include <string>
-
-int s2c_set_error(int code, const std::string &msg);
-template <class F>
-static int s2c_guarded(F &&f) {   // (as in s2c_host.cpp: no exception crosses the C-ABI)
-    try {
-        return f();
-    } catch (const std::bad_alloc &) {
-        return s2c_set_error(S2C_ERR_LIMIT, "out of host memory");
-    } catch (const std::exception &e) {
-        return s2c_set_error(S2C_ERR_IO, std::string("host exception: ") + e.what());
-    }
-}
+#include "s2c_host_internal.h"
 
 #include <zlib.h>
-
-#include <algorithm>
-#include <cstdio>
-#include <cstring>
-#include <functional>
-#include <string>
-#include <vector>
-
-int s2c_set_error(int code, const std::string &msg);
 
 namespace {
 struct Rng {

@@ -668,7 +668,7 @@ __device__ __forceinline__ void tile_epilogue_fast(const D &d, uint32_t tile, co
 // ======================================================================= k_tile
 // One workgroup per work item = (tile [a, b) of ≤ 32·NWP positions, its layers [l0, l1)).
 // The tile's WINDOW — the short pieces starting in the kwin words before it and in it — is
-// cut into nl LAYERS (host plan, s2c_host.cpp plan_layers): layer ℓ takes from every start
+// cut into nl LAYERS (host plan, s2c_plan.cpp plan_layers): layer ℓ takes from every start
 // word s of the window (a SEGMENT) its pieces [ps[s] + n_s·ℓ/nl, ps[s] + n_s·(ℓ+1)/nl), so
 // every layer reaches every word of the tile alike.  Each WAVE of the workgroup takes every
 // WV-th layer of the item into its own LDS chunk and runs it start to end with no

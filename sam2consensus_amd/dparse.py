@@ -40,7 +40,7 @@ BLOCK = 64 << 20          # bytes of SAM text per block
 NO_BLOCK = 1 << 56        # "no failing block" (block keys: below 2^48)
 BIN_SHIFT = 8             # read-start histogram bins of 256 positions
 DENSE_DEPTH = 48.0        # at or below this mean depth: 1024-position dense tiles
-E_TARGET = 262144.0       # aligned bases per deep tile (the planner's, s2c_host.cpp)
+E_TARGET = 262144.0       # aligned bases per deep tile (the planner's, s2c_plan.cpp)
 
 
 class BlockParser(Parser):
@@ -299,7 +299,7 @@ def file_blocks(filename, rank, world, block=BLOCK, group=None):
 
 
 def tile_width_for(depth):
-    """Fixed tile width from the mean depth, as the planner chooses (s2c_host.cpp tiles)."""
+    """Fixed tile width from the mean depth, as the planner chooses (s2c_plan.cpp tile_widths)."""
     if depth <= DENSE_DEPTH:
         return 1024
     w = int(np.ceil(E_TARGET / depth))

@@ -234,7 +234,7 @@ def check_plan(hb):
     assert set(np.nonzero((fl & 16) != 0)[0].tolist()) == by_slot
     assert set(hb.rlist.tolist()) == set(np.nonzero(((fl & 16) != 0) | ((fl & PF_INS) != 0))[0].tolist())
     # (ABI 13) rlist's run prefix: what s2c_reads walks when k_tile's walk-queue variant records
-    # its finish tiles' short-motif events itself (s2c_host.cpp mark_runs)
+    # its finish tiles' short-motif events itself (s2c_plan.cpp mark_runs)
     assert bool(i.walk_queue) == (i.n_walked > 0 and 32 * i.n_walked >= i.n_pieces and i.tile_max <= 1024)
     wq = bool(i.tile_events)
     assert wq <= bool(i.walk_queue)
@@ -283,7 +283,7 @@ def layer_ranges(hb, t, nl=None):
     p0 = ps[S0:W1]
     cnt = ps[S0 + 1:W1 + 1] - p0
     nl = int(row[19]) if nl is None else nl
-    rot = (np.arange(S0, W1, dtype=np.uint64) * np.uint64(2654435761)) % np.uint64(nl)   # s2c_host.cpp layer_rot
+    rot = (np.arange(S0, W1, dtype=np.uint64) * np.uint64(2654435761)) % np.uint64(nl)   # s2c_plan.cpp layer_rot
     rot = rot.astype(np.int64)
     return S0, W0, W1, [(p0 + (cnt * l + rot) // nl, p0 + (cnt * (l + 1) + rot) // nl) for l in range(nl)]
 

@@ -108,12 +108,19 @@ def test_long_reads_and_wrap_pieces():
     assert got == o.run_case(sam, ["-d", "1"])["files"]
 
 
-ARRAYS = ("pc", "ops", "bq", "bx", "rs", "tiles", "items", "dense", "deep", "lp", "wtile")
+# every array s2c_batch_arrays_get returns: the device arrays and the layered windows
+ARRAYS = ("pc", "ops", "bq", "bx", "rs", "tiles", "items", "dense", "deep", "lp", "wtile",
+          "rlist", "ps", "px", "dwin", "dpc", "lly", "lpc", "lops", "lbq", "lbx", "lpx")
+
+
+def _arrays(hb):
+    hb.ensure_layers(dense=True)   # (the l* arrays exist once the layers are built: every tile's)
+    return [(n, np.ascontiguousarray(getattr(hb, n))) for n in ARRAYS]
 
 
 def _same(a, b):
-    for n in ARRAYS:
-        assert (np.asarray(getattr(a, n)) == np.asarray(getattr(b, n))).all(), n
+    for (n, x), (_, y) in zip(_arrays(a), _arrays(b)):
+        assert np.array_equal(x, y), n
 
 
 def test_text_and_file_and_gzip_parse_agree():
@@ -243,8 +250,8 @@ def _batch_digest(path, maxdel_active):
     except (KeyError, IndexError, ValueError, ZeroDivisionError, OverflowError) as e:
         return type(e).__name__
     h = hashlib.sha256()
-    for n in ARRAYS:
-        h.update(np.ascontiguousarray(getattr(hb, n)).tobytes())
+    for _, a in _arrays(hb):
+        h.update(a.tobytes())
     i = hb.info
     h.update(repr((i.lines_total, i.reads_mapped, i.aligned_bases, i.query_bases, i.header_lines)).encode())
     return h.hexdigest()
@@ -256,8 +263,8 @@ def _text_digest(text, maxdel_active):
     except (KeyError, IndexError, ValueError, ZeroDivisionError, OverflowError) as e:
         return type(e).__name__
     h = hashlib.sha256()
-    for n in ARRAYS:
-        h.update(np.ascontiguousarray(getattr(hb, n)).tobytes())
+    for _, a in _arrays(hb):
+        h.update(a.tobytes())
     i = hb.info
     h.update(repr((i.lines_total, i.reads_mapped, i.aligned_bases, i.query_bases, i.header_lines)).encode())
     return h.hexdigest()
@@ -320,7 +327,7 @@ def test_parallel_file_parse_equals_sequential(tmp_path, monkeypatch):
 
 
 def test_worker_pools_concurrent_and_forked(tmp_path, monkeypatch):
-    """The host's persistent worker pools (s2c_host.cpp WorkerPool): parses and plans run from
+    """The host's persistent worker pools (s2c_host_internal.h WorkerPool): parses and plans run from
     several Python threads at once (a busy pool hands the second caller threads of its own)
     and from a forked child after the parent used the pools — each one the same batch as a
     serial parse."""
@@ -724,23 +731,25 @@ def test_dense_needs_compact_records():
 
 
 def test_host_code_under_sanitizers(tmp_path):
-    """The host library's parse / plan / streaming paths (s2c_host.cpp) built with AddressSanitizer
-    and UndefinedBehaviorSanitizer (host code only: no GPU code is sanitized) and driven by
-    tests/native/*_drive.cpp over plain and BGZF inputs, 1 and 4 parse threads: clean."""
+    """The host library's parse / plan / streaming paths (every host source, csrc/*.cpp) built with
+    AddressSanitizer and UndefinedBehaviorSanitizer (host code only: no GPU code is sanitized) and driven
+    by tests/native/*_drive.cpp over plain and BGZF inputs, 1 and 4 parse threads: clean."""
+    import glob
     import shutil
     if not shutil.which("g++"):
         pytest.skip("g++ not found")
-    src = os.path.join(ROOT, "sam2consensus_amd", "csrc", "s2c_host.cpp")
-    san = ["-fsanitize=address,undefined", "-fno-omit-frame-pointer", "-fno-sanitize-recover=undefined"]
-    obj = str(tmp_path / "host.o")
-    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-I" + os.path.join(ROOT, "include")] + san + ["-c", src, "-o", obj],
-                   check=True, timeout=600)
+    srcs = sorted(glob.glob(os.path.join(ROOT, "sam2consensus_amd", "csrc", "*.cpp")))   # (the Makefile's HOSTSRC)
+    assert len(srcs) > 1
+    cxx = ["g++", "-O1", "-g", "-std=c++17", "-I" + os.path.join(ROOT, "include"),
+           "-fsanitize=address,undefined", "-fno-omit-frame-pointer", "-fno-sanitize-recover=undefined"]
+    objs = [str(tmp_path / (os.path.basename(s)[:-4] + ".o")) for s in srcs]
+    procs = [subprocess.Popen(cxx + ["-c", s, "-o", ob]) for s, ob in zip(srcs, objs)]
+    assert [p.wait(timeout=600) for p in procs] == [0] * len(srcs)
     exe = {}
     for name in ("parse_drive", "stream_drive"):
         exe[name] = str(tmp_path / name)
-        subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-I" + os.path.join(ROOT, "include")] + san +
-                       [os.path.join(ROOT, "tests", "native", name + ".cpp"), obj, "-o", exe[name], "-lz", "-lpthread"],
-                       check=True, timeout=300)
+        subprocess.run(cxx + [os.path.join(ROOT, "tests", "native", name + ".cpp")] + objs +
+                       ["-o", exe[name], "-lz", "-lpthread"], check=True, timeout=300)
     inputs = {"c2": str(tmp_path / "c2.sam"), "c3": str(tmp_path / "c3.sam.gz"), "c5": str(tmp_path / "c5.sam")}
     configs.synth_write("c2", inputs["c2"], scale=0.05)
     configs.synth_write("c3", inputs["c3"], scale=0.005)
