@@ -14,7 +14,7 @@ LINK     = $(HIPCC) -shared -fPIC --offload-arch=$(ARCH) $^ -lz -lpthread -o $@
 # the one list of host sources (every csrc/*.cpp) and of kernel sources
 HOSTSRC  = $(wildcard $(SRC)/*.cpp)
 HOSTOBJ  = $(HOSTSRC:$(SRC)/%.cpp=$(BUILD)/%.o)
-KERNELS  = s2c_reads s2c_tile s2c_dense s2c_bodies s2c_table
+KERNELS  = s2c_reads s2c_tile s2c_dense s2c_bodies s2c_table s2c_sites
 KOBJ     = $(KERNELS:%=$(BUILD)/%.o)
 
 all: $(OUT)
@@ -23,7 +23,7 @@ $(BUILD)/%.o: $(SRC)/%.cpp $(SRC)/s2c_host_internal.h include/s2c.h | $(BUILD)
 	$(CXX) $(CXXFLAGS) -c $< -o $@
 
 # (every kernel's resource remarks checked: a spill fails the build, scripts/check_spills.py)
-$(BUILD)/%.o: $(SRC)/%.hip $(SRC)/s2c_common.h include/s2c.h scripts/check_spills.py | $(BUILD)
+$(BUILD)/%.o: $(SRC)/%.hip $(SRC)/s2c_common.h $(SRC)/s2c_text.h include/s2c.h scripts/check_spills.py | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -Rpass-analysis=kernel-resource-usage -c $< -o $@ 2> $(BUILD)/$*.usage || { cat $(BUILD)/$*.usage; exit 1; }
 	python3 scripts/check_spills.py $(BUILD)/$*.usage || { rm -f $@; exit 1; }
 
@@ -52,7 +52,7 @@ poison: sam2consensus_amd/libs2c_poison.so
 variant: sam2consensus_amd/libs2c_$(V).so
 
 define DIAG_RULES
-$$(BUILD)/%_$(1).o: $$(SRC)/%.hip $$(SRC)/s2c_common.h include/s2c.h FORCE | $$(BUILD)
+$$(BUILD)/%_$(1).o: $$(SRC)/%.hip $$(SRC)/s2c_common.h $$(SRC)/s2c_text.h include/s2c.h FORCE | $$(BUILD)
 	$$(HIPCC) $$(HIPFLAGS) $$(DEFS_$(1)) -c $$< -o $$@
 sam2consensus_amd/libs2c_$(1).so: $$(HOSTOBJ) $$(filter-out $$(DIAG_$(1):%=$$(BUILD)/%.o),$$(KOBJ)) $$(DIAG_$(1):%=$$(BUILD)/%_$(1).o)
 	$$(LINK)

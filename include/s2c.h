@@ -542,6 +542,27 @@ int s2c_table_len(const uint32_t *counts, int64_t padded_len, const int64_t *blo
 int s2c_table_write(const uint32_t *counts, int64_t padded_len, const int64_t *blocks, const int64_t *offs,
                     int64_t n, uint8_t *dst, int64_t dst_len, void *stream);
 
+/* Sparse tables of mixed sites as text (the CLI's --variants; csrc/s2c_sites.hip), from the
+ * same counts and blocks as the count tables.  With cov = Σc (64-bit), rank(s) = #{s' :
+ * c[s'] > c[s] or (c[s'] == c[s] and s' < s)}, major the symbol of rank 0 and alt = cov −
+ * c[major], a position is a site iff cov >= min_cov, alt >= min_alt and (double)alt >=
+ * min_frac · (double)cov (one fp64 product).  A site's line is the count table's plus three
+ * fields, "P\tCOV\tn-\tnA\tnC\tnG\tnN\tnT\tM\tALT\t0.dddd\n": M the major symbol's character,
+ * ALT the other symbols with a non-zero count in rank order, dddd = ⌊alt · 10000 / cov⌋; at
+ * most 104 bytes.  s2c_sites_mark (min_cov >= 1, min_alt >= 1, 0 <= min_frac <= 1) writes
+ * mask[⌈padded_len / 64⌉]: bit g & 63 of word g >> 6 set iff position g is a site, bits at or
+ * past padded_len zero.  s2c_sites_len and s2c_sites_write are s2c_table_len and
+ * s2c_table_write over the positions the mask selects: lens[i] the exact bytes of block i's
+ * site lines, block i's lines in position order to dst[offs[i], offs[i+1]) and no byte outside
+ * it, the same blocks skipped.  All three are asynchronous on stream and allocate nothing;
+ * they add no struct field (ABI 14 stands). */
+int s2c_sites_mark(const uint32_t *counts, int64_t padded_len, int64_t min_cov, int64_t min_alt, double min_frac,
+                   uint64_t *mask, void *stream);
+int s2c_sites_len(const uint32_t *counts, int64_t padded_len, const uint64_t *mask, const int64_t *blocks, int64_t n,
+                  int64_t *lens, void *stream);
+int s2c_sites_write(const uint32_t *counts, int64_t padded_len, const uint64_t *mask, const int64_t *blocks,
+                    const int64_t *offs, int64_t n, uint8_t *dst, int64_t dst_len, void *stream);
+
 /* Diagnostics (tests only, not part of the product path): k_reads over every piece, then
  * every tile's counts stored to d->counts ([6][padded_len] u32) and no vote. */
 int s2c_pileup_counts(const s2c_dev *d, void *stream);

@@ -50,7 +50,41 @@ def build_parser():
                         "with the position, the coverage and the counts of -, A, C, G, N, T (tab-separated; "
                         "insertion columns are not part of the table; independent of -c, -m, -f and -n). "
                         "Not available with more than one process or with S2C_STREAM")
+    p.add_argument("--variants", action="store_true", dest="variants", default=False,
+                   help="Also write REF__PREFIX.variants.tsv beside each FASTA file: the --counts line of every "
+                        "position where a minority is present (coverage at least max(-m, 1), at least "
+                        "--min-alt-reads reads not of the major symbol, and at least --min-alt-frac of the "
+                        "coverage), followed by the major symbol, the other symbols present in order of their "
+                        "counts, and the minority's share of the coverage; all six symbols take part, - and N "
+                        "included; insertion columns are not part of the table. "
+                        "Not available with more than one process or with S2C_STREAM")
+    p.add_argument("--min-alt-reads", action="store", dest="min_alt_reads", type=int, default=None, metavar="N",
+                   help="With --variants: least number of reads not of the major symbol at a site, default=2")
+    p.add_argument("--min-alt-frac", action="store", dest="min_alt_frac", type=float, default=None, metavar="F",
+                   help="With --variants: least share of the coverage not of the major symbol at a site, "
+                        "between 0 and 1, default=0.05")
     return p
+
+
+MIN_ALT_READS, MIN_ALT_FRAC = 2, 0.05
+
+
+def variants_of(parser, args):
+    """(min_alt, min_frac) of --variants or None; a bad value, or either option without
+    --variants, is the parser's error (exit status 2)."""
+    n, f = args.min_alt_reads, args.min_alt_frac
+    if not args.variants:
+        for opt, v in (("--min-alt-reads", n), ("--min-alt-frac", f)):
+            if v is not None:
+                parser.error(opt + " needs --variants")
+        return None
+    n = MIN_ALT_READS if n is None else n
+    f = MIN_ALT_FRAC if f is None else f
+    if n < 1:
+        parser.error("--min-alt-reads must be at least 1")
+    if not 0.0 <= f <= 1.0:   # (a NaN too)
+        parser.error("--min-alt-frac must be between 0 and 1")
+    return n, f
 
 
 class RunResult:
@@ -69,10 +103,12 @@ class RunResult:
 
 
 def consensus_batch(hb, thresholds, prefix, min_depth=1, fill=b"-", nchar=0, device=None, timings=None,
-                    counts=False):
+                    counts=False, variants=None):
     """Device pipeline on a parsed HostBatch → {``REF__PREFIX.fasta``: bytes}; with ``counts``
-    also the ``REF__PREFIX.counts.tsv`` count tables (table.py), after the FASTA entries — the
-    run then takes the counts route (``Workspace.run_with_counts``)."""
+    also the ``REF__PREFIX.counts.tsv`` count tables (table.py), after the FASTA entries, and
+    with ``variants`` = (min_alt, min_frac) the ``REF__PREFIX.variants.tsv`` tables of mixed
+    sites (coverage at least max(min_depth, 1)) after those — the run then takes the counts
+    route (``Workspace.run_with_tables``)."""
     import torch
 
     from .engine import _UPLOADERS, DeviceBatch, Workspace, needs_dense_layers, to_host
@@ -80,9 +116,10 @@ def consensus_batch(hb, thresholds, prefix, min_depth=1, fill=b"-", nchar=0, dev
 
     t = timings if timings is not None else {}
     t0 = time.perf_counter()
-    db = DeviceBatch(hb, device, dense_layers=needs_dense_layers(fill, counts))
+    tables = bool(counts) or variants is not None
+    db = DeviceBatch(hb, device, dense_layers=needs_dense_layers(fill, tables))
     t1 = time.perf_counter()
-    ws = Workspace(db, thresholds, min_depth, fill, keep_counts=bool(counts))
+    ws = Workspace(db, thresholds, min_depth, fill, keep_counts=tables)
     torch.cuda.synchronize(db.device)
     t["h2d"] = time.perf_counter() - t0
     t["h2d_issue"] = t1 - t0   # (layers + pinned staging + copies issued; the rest: workspace + drain)
@@ -90,8 +127,9 @@ def consensus_batch(hb, thresholds, prefix, min_depth=1, fill=b"-", nchar=0, dev
     if up is not None:   # (the pinned ring's cumulative host seconds: alloc, wait, pack, issue)
         t.update(("h2d_up_" + k, v) for k, v in up.timing.items())
     t0 = time.perf_counter()
-    if counts:
-        toffs, ttext = ws.run_with_counts()
+    if tables:
+        sites = (max(int(min_depth), 1),) + tuple(variants) if variants is not None else None
+        ctab, stab = ws.run_with_tables(counts=bool(counts), sites=sites)
     else:
         ws.run()
     torch.cuda.synchronize(db.device)
@@ -105,9 +143,12 @@ def consensus_batch(hb, thresholds, prefix, min_depth=1, fill=b"-", nchar=0, dev
     files = {}
     for name, recs in fastas.items():
         files[name.encode("latin-1") + b"__" + pre + b".fasta"] = render(recs, nchar)
-    if counts:   # (after build_records: a vote error raises and no file is returned)
-        from .table import table_files
-        files.update(table_files(hb, pre, toffs, to_host(ttext)))
+    if tables:   # (after build_records: a vote error raises and no file is returned)
+        from .table import SITES_HEADER, SITES_SUFFIX, table_files
+        if counts:
+            files.update(table_files(hb, pre, ctab[0], to_host(ctab[1])))
+        if variants is not None:
+            files.update(table_files(hb, pre, stab[0], to_host(stab[1]), SITES_HEADER, SITES_SUFFIX))
     t["format"] = time.perf_counter() - t0
     return files
 
@@ -217,8 +258,9 @@ def consensus_batch_hip(sess, hb, thresholds, prefix, min_depth=1, fill=b"-", nc
     return files
 
 
-def _consensus_files_counts(filename, thresholds, prefix, min_depth, fill, nchar, maxdel_active, device, log):
-    """consensus_files with the count tables: the torch engine path (consensus_batch)."""
+def _consensus_files_tables(filename, thresholds, prefix, min_depth, fill, nchar, maxdel_active, device, log,
+                            counts, variants):
+    """consensus_files with the count or variant tables: the torch engine path (consensus_batch)."""
     import torch
 
     from . import _lib
@@ -243,19 +285,21 @@ def _consensus_files_counts(filename, thresholds, prefix, min_depth, fill, nchar
     t["parse"] = time.perf_counter() - t0
     if log:
         _log_summary(log, hb.info)
-    files = consensus_batch(hb, thresholds, prefix, min_depth, fill, nchar, dev, t, counts=True)
+    files = consensus_batch(hb, thresholds, prefix, min_depth, fill, nchar, dev, t, counts=counts, variants=variants)
     return RunResult(files, t, hb.info, hb.free_async())
 
 
 def consensus_files(filename, thresholds, prefix, min_depth=1, fill=b"-", nchar=0, maxdel_active=True,
-                    device=None, log=None, counts=False):
+                    device=None, log=None, counts=False, variants=None):
     """Run the whole pipeline on one SAM/SAM.gz file; returns a RunResult whose
     ``files`` maps ``REF__PREFIX.fasta`` → content bytes (nothing written).  The device side
     runs through the HIP runtime directly (hiprun.py): this path never imports PyTorch.
-    With ``counts`` the files also hold the ``REF__PREFIX.counts.tsv`` count tables, and the
-    run goes through the torch engine path instead (``consensus_batch(counts=True)``)."""
-    if counts:
-        return _consensus_files_counts(filename, thresholds, prefix, min_depth, fill, nchar, maxdel_active, device, log)
+    With ``counts`` the files also hold the ``REF__PREFIX.counts.tsv`` count tables, with
+    ``variants`` = (min_alt, min_frac) the ``REF__PREFIX.variants.tsv`` tables of mixed sites,
+    and the run goes through the torch engine path instead (``consensus_batch``)."""
+    if counts or variants is not None:
+        return _consensus_files_tables(filename, thresholds, prefix, min_depth, fill, nchar, maxdel_active, device, log,
+                                       bool(counts), variants)
     from .batch import Parser
     from .hiprun import Session, device_index
 
@@ -287,19 +331,24 @@ def consensus_files(filename, thresholds, prefix, min_depth=1, fill=b"-", nchar=
     return RunResult(files, t, hb.info, hb.free_async())
 
 
-def run_text(sam_text, argv, device=None, counts=False):
+def run_text(sam_text, argv, device=None, counts=False, variants=None):
     """Library entry for tests: SAM text + CLI args (without -i) → (status, {fname: str}).
     status is "ok" or the reference's exception class name; nothing touches the disk.
-    ``counts`` (or ``--counts`` among the args): the count tables too."""
+    ``counts`` (or ``--counts`` among the args): the count tables too; ``variants`` =
+    (min_alt, min_frac) (or ``--variants`` and its options among the args): the tables of
+    mixed sites too."""
     from .batch import parse_text
 
-    args = build_parser().parse_args(["-i", "in.sam"] + list(argv))
+    parser = build_parser()
+    args = parser.parse_args(["-i", "in.sam"] + list(argv))
+    variants = variants_of(parser, args) or variants
     try:
         thresholds = [float(i) for i in args.thresholds.split(",")]
         prefix = args.prefix or "in"
         hb = parse_text(sam_text, not isinstance(args.maxdel, str), 150)
         files = consensus_batch(hb, thresholds, os.fsencode(prefix), args.min_depth,
-                                os.fsencode(args.fill), args.n, device, counts=bool(counts or args.counts))
+                                os.fsencode(args.fill), args.n, device, counts=bool(counts or args.counts),
+                                variants=variants)
     except (KeyError, IndexError, ValueError, ZeroDivisionError, OverflowError) as e:
         return type(e).__name__, {}
     return "ok", {k.decode("latin-1"): v.decode("latin-1") for k, v in files.items()}
@@ -368,11 +417,13 @@ def consensus_files_sharded(filename, thresholds, prefix, min_depth, fill, nchar
 def main(argv=None):
     parser = build_parser()
     args = parser.parse_args(argv)
-    if args.counts:   # (refused before a folder is made or a device touched)
-        if _dist_env()[0] > 1:
-            parser.error("--counts is not available with more than one process (WORLD_SIZE > 1)")
-        if os.environ.get("S2C_STREAM"):
-            parser.error("--counts is not available with streamed batches (S2C_STREAM)")
+    variants = variants_of(parser, args)
+    for flag, on in (("--counts", args.counts), ("--variants", variants is not None)):
+        if on:   # (refused before a folder is made or a device touched)
+            if _dist_env()[0] > 1:
+                parser.error(flag + " is not available with more than one process (WORLD_SIZE > 1)")
+            if os.environ.get("S2C_STREAM"):
+                parser.error(flag + " is not available with streamed batches (S2C_STREAM)")
     filename = args.filename
     thresholds = [float(i) for i in args.thresholds.split(",")]                # :117-118
     if args.prefix == "":
@@ -403,7 +454,7 @@ def main(argv=None):
         else:
             res = consensus_files(filename, thresholds, os.fsencode(prefix), args.min_depth,
                                   os.fsencode(args.fill), args.n, maxdel_active, log=lambda s: print(s),
-                                  counts=args.counts)
+                                  counts=args.counts, variants=variants)
             files = res.files
     tables = []
     for fname, body in files.items():                                             # :411-424
@@ -413,6 +464,8 @@ def main(argv=None):
         shown = os.fsdecode(path)
         if args.counts and fname.endswith(b".counts.tsv"):
             tables.append("Count table saved for " + os.fsdecode(fname[: fname.rfind(b"__")]) + " in: " + shown)
+        elif variants is not None and fname.endswith(b".variants.tsv"):   # (the files come after the count tables)
+            tables.append("Variant table saved for " + os.fsdecode(fname[: fname.rfind(b"__")]) + " in: " + shown)
         elif len(thresholds) == 1:
             print("Consensus sequence at " + str(int(thresholds[0] * 100)) + "% saved for " +
                   os.fsdecode(fname[: fname.rfind(b"__")]) + " in: " + shown)

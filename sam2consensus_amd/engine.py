@@ -393,21 +393,61 @@ class Workspace:
                                     total, st))
         return offs, text[:total]
 
-    def run_with_counts(self):
-        """``run()`` through the counts route, with the count tables: every tile's counts
+    def sites_table(self, min_cov=1, min_alt=2, min_frac=0.05):
+        """The filled ``counts`` as the text of the tables of mixed sites (table.py;
+        s2c_sites_mark into a bit per position, then s2c_sites_len, the prefix sum and
+        s2c_sites_write over the set bits, on the current stream): the return shape and the
+        preconditions of ``counts_table`` — tile k's site lines at [offs[k], offs[k+1])."""
+        if not self.keep_counts or self.tile_range is not None:
+            raise ValueError("sites_table needs Workspace(keep_counts=True) over the whole batch")
+        if not self._counts_filled:
+            raise ValueError("sites_table needs filled counts (accumulate / pileup_counts; s2c_consensus zeroes them)")
+        i = self.db.info
+        dev = self.db.device
+        nt = int(i.n_tiles)
+        if nt == 0:
+            return np.zeros(1, dtype=np.int64), torch.empty(0, dtype=torch.uint8, device=dev)
+        st = self.stream_handle()
+        blocks = self._table_blocks()
+        mask = torch.empty(max((int(i.padded_len) + 63) // 64, 1), dtype=torch.int64, device=dev)
+        offs_d = torch.zeros(nt + 1, dtype=torch.int64, device=dev)
+        lens = torch.empty(nt, dtype=torch.int64, device=dev)
+        L.check(lib.s2c_sites_mark(_ptr(self.counts), i.padded_len, int(min_cov), int(min_alt), float(min_frac),
+                                   _ptr(mask), st))
+        L.check(lib.s2c_sites_len(_ptr(self.counts), i.padded_len, _ptr(mask), _ptr(blocks), nt, _ptr(lens), st))
+        torch.cumsum(lens, 0, out=offs_d[1:])
+        offs = offs_d.cpu().numpy()
+        total = int(offs[-1])
+        text = torch.empty(max(total, 16), dtype=torch.uint8, device=dev)
+        L.check(lib.s2c_sites_write(_ptr(self.counts), i.padded_len, _ptr(mask), _ptr(blocks), _ptr(offs_d), nt,
+                                    _ptr(text), total, st))
+        return offs, text[:total]
+
+    def run_with_tables(self, counts=True, sites=None):
+        """``run()`` through the counts route, with either or both tables: every tile's counts
         stored (s2c_accumulate on zeroed counts, the insertion tables kept), formatted as text
-        (``counts_table`` — before the vote, which leaves the counts zero), then every tile
-        voted from them (``vote_all``); ``fetch()`` yields the FASTA results as after
-        ``run()``.  Returns counts_table()'s (offs, device text)."""
+        (before the vote, which leaves the counts zero), then every tile voted from them
+        (``vote_all``); ``fetch()`` yields the FASTA results as after ``run()``.  ``counts``:
+        the count tables; ``sites`` (min_cov, min_alt, min_frac): the tables of mixed sites.
+        Returns (counts_table() or None, sites_table(*sites) or None): a table not asked for
+        is not formatted."""
         if not self.keep_counts:
-            raise ValueError("run_with_counts needs Workspace(keep_counts=True)")
+            raise ValueError("run_with_tables needs Workspace(keep_counts=True)")
         self._counts_ready()
         # (set first: if a stage raises, a reused workspace zeroes its counts before its next run)
         self._counts_filled = True
         self.accumulate(keep_tables=True)
-        table = self.counts_table()
+        table = self.counts_table() if counts else None
+        stable = self.sites_table(*sites) if sites is not None else None
         self.vote_all()
-        return table
+        return table, stable
+
+    def run_with_counts(self):
+        """``run_with_tables`` with the count tables alone.  Returns counts_table()'s (offs,
+        device text)."""
+        if not self.keep_counts:
+            raise ValueError("run_with_counts needs Workspace(keep_counts=True)")
+        return self.run_with_tables(counts=True)[0]
 
     def pileup_counts(self):
         """Diagnostic: k_reads, then every tile's counts stored to `counts` (no vote); needs

@@ -6,6 +6,17 @@ in ``-ACGNT`` order, tab-separated plain decimal.  Insertion columns (:262-311) 
 of the table.  The device formats the text (csrc/s2c_table.hip, ``Workspace.counts_table``);
 ``format_rows`` is the same format in plain Python — the tests' model, and enough for small
 inputs on the host.
+
+Tables of mixed sites (``--variants``): ``REF__PREFIX.variants.tsv``, the count table's lines of
+the positions where a minority is present, each with three more fields.  With ``cov`` the sum
+of the six counts, ``rank(s) = #{s' : c[s'] > c[s] or (c[s'] == c[s] and s' < s)}``, ``major``
+the symbol of rank 0 (ties: the earlier symbol in ``-ACGNT``) and ``alt = cov - c[major]``, a
+position is a site iff ``cov >= min_cov``, ``alt >= min_alt`` and ``float(alt) >= min_frac *
+float(cov)`` (one fp64 product and compare).  Its line ends ``\tM\tALT\t0.dddd``: the major
+symbol, the other symbols with a non-zero count in rank order, ``dddd = alt * 10000 // cov``.
+All six symbols take part, ``-`` and ``N`` included, as in the vote; insertion columns do not.
+The device selects and formats (csrc/s2c_sites.hip, ``Workspace.sites_table``); ``site_mask``
+and ``format_sites`` are the model.
 """
 from __future__ import annotations
 
@@ -13,6 +24,9 @@ import numpy as np
 
 HEADER = b"pos\tcov\t-\tA\tC\tG\tN\tT\n"
 SUFFIX = b".counts.tsv"
+SITES_HEADER = b"pos\tcov\t-\tA\tC\tG\tN\tT\tmajor\talt\taf\n"
+SITES_SUFFIX = b".variants.tsv"
+SYMBOLS = "-ACGNT"
 
 
 def format_rows(counts_6xL, p0=1):
@@ -27,8 +41,42 @@ def format_rows(counts_6xL, p0=1):
     return "".join("%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\n" % tuple(r) for r in rows.tolist()).encode("ascii")
 
 
-def table_files(hb, prefix, offs, body):
-    """{``REF__PREFIX.counts.tsv``: bytes} from ``Workspace.counts_table``'s text on the host:
+def _c6(counts_6xL):
+    c = np.asarray(counts_6xL)
+    if c.ndim != 2 or c.shape[0] != 6:
+        raise ValueError("counts must be [6][L]")
+    return c
+
+
+def site_mask(counts_6xL, min_cov=1, min_alt=2, min_frac=0.05):
+    """bool[L]: the positions of counts[6][L] that are sites.  Integers in int64 (cov < 2^35),
+    the last test in float64 as the device's: both operands below 2^53, so the conversions are
+    exact and the one product rounds as Python's ``min_frac * float(cov)`` does."""
+    c = _c6(counts_6xL).astype(np.int64)
+    cov = c.sum(axis=0)
+    alt = cov - (c.max(axis=0) if c.shape[1] else cov)
+    return (cov >= int(min_cov)) & (alt >= int(min_alt)) & (alt.astype(np.float64) >= np.float64(min_frac) * cov.astype(np.float64))
+
+
+def format_sites(counts_6xL, p0=1, min_cov=1, min_alt=2, min_frac=0.05):
+    """The site lines (no header) of counts[6][L], position ``p0`` printed for column 0."""
+    c = _c6(counts_6xL)
+    out = []
+    for j in np.flatnonzero(site_mask(c, min_cov, min_alt, min_frac)).tolist():
+        n = [int(v) for v in c[:, j]]
+        cov = sum(n)
+        order = sorted(range(6), key=lambda s: (-n[s], s))   # by rank
+        alt = cov - n[order[0]]
+        out.append("%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%s\t%s\t0.%04d\n" % (
+            int(p0) + j, cov, n[0], n[1], n[2], n[3], n[4], n[5], SYMBOLS[order[0]],
+            "".join(SYMBOLS[s] for s in order[1:] if n[s]), alt * 10000 // cov))
+    return "".join(out).encode("ascii")
+
+
+def table_files(hb, prefix, offs, body, header=HEADER, suffix=SUFFIX):
+    """{``REF__PREFIX.counts.tsv``: bytes} from ``Workspace.counts_table``'s text on the host
+    (with ``SITES_HEADER`` and ``SITES_SUFFIX``: the ``.variants.tsv`` files from
+    ``Workspace.sites_table``'s; a reference without a site gets the header alone):
     ``offs[k]`` the byte offset of tile k's rows in ``body`` (n_tiles + 1 entries; tiles are
     emitted reference by reference).  One table per reference with Σcoverage > 0 (the
     reference's own pruning rule, :334-341 — not the FASTA records' keep rule)."""
@@ -39,5 +87,5 @@ def table_files(hb, prefix, offs, body):
             continue
         f0, n = int(hb.ref_first_block[r]), int(hb.ref_nblocks[r])
         a, b = int(offs[f0]), int(offs[f0 + n])
-        files[hb.names[r].encode("latin-1") + b"__" + pre + SUFFIX] = HEADER + body[a:b]
+        files[hb.names[r].encode("latin-1") + b"__" + pre + suffix] = header + body[a:b]
     return files
