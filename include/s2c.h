@@ -563,6 +563,39 @@ int s2c_sites_len(const uint32_t *counts, int64_t padded_len, const uint64_t *ma
 int s2c_sites_write(const uint32_t *counts, int64_t padded_len, const uint64_t *mask, const int64_t *blocks,
                     const int64_t *offs, int64_t n, uint8_t *dst, int64_t dst_len, void *stream);
 
+/* Runs of equal coverage as text (the CLI's --depth and --lowcov; csrc/s2c_runs.hip), from the
+ * same counts and blocks as the count tables.  With cov = Σc (64-bit) the class of a position
+ * is cov itself when cut == 0 and the predicate cov < cut when cut >= 1; a run is a maximal
+ * stretch of one class inside its reference.  s2c_runs_mark (cut >= 0) writes
+ * mask[⌈padded_len / 64⌉]: bit g & 63 of word g >> 6 set iff class(g) != class(g − 1), bit 0
+ * set, bits at or past padded_len zero; it knows nothing of blocks or references.
+ * s2c_runs_len and s2c_runs_write take the blocks {a, b, p0} of the count tables and refs =
+ * device [n][2] int64 {s, e}, the global range [s, e) of the reference block i lies in; a block
+ * is valid iff 0 <= s <= a <= b <= e <= padded_len, 0 <= p0 and p0 + (e − a) <= 10^10.  The
+ * run starts of a block are the set mask bits in [a, b), the bit at g == s forced on when
+ * a == s (references start at multiples of 64 behind zero-count padding).  A run belongs to the
+ * block that holds its start; its end is the next set bit, clamped to e — possibly several
+ * blocks on, which then have no start and give no byte — so the text does not depend on how
+ * the blocks cut a reference.  With S = p0 + (g − a) and E = p0 + (end − a) − 1 the printed
+ * first and last position, a run's line is "S\tE\tCOV\n" when cut == 0 (at most 34 bytes) and
+ * "S\tE\n" when cut >= 1, for the runs whose predicate holds alone (at most 22 bytes).
+ * s2c_runs_len writes lens[i], the exact bytes of block i's lines, and, when cut == 0,
+ * stats[i][6] int64 {runs, covered, passed, sumcov, mincov, maxcov} over the runs that start in
+ * block i, each from the runs' (length, cov): positions with cov >= 1, with cov >= min_cov
+ * (min_cov >= 0), Σ length · cov, the least and largest cov; {0, 0, 0, 0, INT64_MAX, −1} for a
+ * block without a start.  A block outside the bounds gets lens[i] = 0 and those empty stats.
+ * With cut >= 1 stats is not written and may be NULL.  s2c_runs_write writes block i's lines in
+ * position order to dst[offs[i], offs[i+1]) and no byte outside it, skipping the blocks
+ * s2c_sites_write skips.  All three are asynchronous on stream and allocate nothing; they add
+ * no struct field (ABI 14 stands). */
+int s2c_runs_mark(const uint32_t *counts, int64_t padded_len, int64_t cut, uint64_t *mask, void *stream);
+int s2c_runs_len(const uint32_t *counts, int64_t padded_len, const uint64_t *mask, const int64_t *blocks,
+                 const int64_t *refs, int64_t n, int64_t cut, int64_t min_cov, int64_t *lens, int64_t *stats,
+                 void *stream);
+int s2c_runs_write(const uint32_t *counts, int64_t padded_len, const uint64_t *mask, const int64_t *blocks,
+                   const int64_t *refs, const int64_t *offs, int64_t n, int64_t cut, uint8_t *dst, int64_t dst_len,
+                   void *stream);
+
 /* Diagnostics (tests only, not part of the product path): k_reads over every piece, then
  * every tile's counts stored to d->counts ([6][padded_len] u32) and no vote. */
 int s2c_pileup_counts(const s2c_dev *d, void *stream);

@@ -121,6 +121,7 @@ EXPORTS = [
     "s2c_workspace_sizes", "s2c_reads", "s2c_pileup", "s2c_consensus", "s2c_run", "s2c_pileup_counts",
     "s2c_gather_bodies_dev", "s2c_plan_set_cus", "s2c_table_len", "s2c_table_write",
     "s2c_sites_mark", "s2c_sites_len", "s2c_sites_write",
+    "s2c_runs_mark", "s2c_runs_len", "s2c_runs_write",
 ]
 
 
@@ -203,6 +204,9 @@ def _load():
         "s2c_sites_mark": (C.c_int, [_VP, C.c_int64, C.c_int64, C.c_int64, C.c_double, _VP, _VP]),
         "s2c_sites_len": (C.c_int, [_VP, C.c_int64, _VP, _VP, C.c_int64, _VP, _VP]),
         "s2c_sites_write": (C.c_int, [_VP, C.c_int64, _VP, _VP, _VP, C.c_int64, _VP, C.c_int64, _VP]),
+        "s2c_runs_mark": (C.c_int, [_VP, C.c_int64, C.c_int64, _VP, _VP]),
+        "s2c_runs_len": (C.c_int, [_VP, C.c_int64, _VP, _VP, _VP, C.c_int64, C.c_int64, C.c_int64, _VP, _VP, _VP]),
+        "s2c_runs_write": (C.c_int, [_VP, C.c_int64, _VP, _VP, _VP, _VP, C.c_int64, C.c_int64, _VP, C.c_int64, _VP]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)

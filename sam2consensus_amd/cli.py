@@ -58,6 +58,17 @@ def build_parser():
                         "counts, and the minority's share of the coverage; all six symbols take part, - and N "
                         "included; insertion columns are not part of the table. "
                         "Not available with more than one process or with S2C_STREAM")
+    p.add_argument("--depth", action="store_true", dest="depth", default=False,
+                   help="Also write REF__PREFIX.depth.tsv beside each FASTA file: one line start, end, cov "
+                        "(tab-separated, 1-based, inclusive) per maximal run of positions with the same coverage, "
+                        "uncovered runs included, and one PREFIX.depth_summary.tsv with a line per reference: "
+                        "its length, the positions with coverage >= 1 and >= max(-m, 1), the sum, least and "
+                        "largest coverage and the number of runs. "
+                        "Not available with more than one process or with S2C_STREAM")
+    p.add_argument("--lowcov", action="store_true", dest="lowcov", default=False,
+                   help="Also write REF__PREFIX.lowcov.tsv beside each FASTA file: one line start, end per "
+                        "maximal run of positions with coverage below max(-m, 1), where the consensus holds "
+                        "the -f character. Not available with more than one process or with S2C_STREAM")
     p.add_argument("--min-alt-reads", action="store", dest="min_alt_reads", type=int, default=None, metavar="N",
                    help="With --variants: least number of reads not of the major symbol at a site, default=2")
     p.add_argument("--min-alt-frac", action="store", dest="min_alt_frac", type=float, default=None, metavar="F",
@@ -103,12 +114,15 @@ class RunResult:
 
 
 def consensus_batch(hb, thresholds, prefix, min_depth=1, fill=b"-", nchar=0, device=None, timings=None,
-                    counts=False, variants=None):
+                    counts=False, variants=None, depth=False, lowcov=False):
     """Device pipeline on a parsed HostBatch → {``REF__PREFIX.fasta``: bytes}; with ``counts``
     also the ``REF__PREFIX.counts.tsv`` count tables (table.py), after the FASTA entries, and
     with ``variants`` = (min_alt, min_frac) the ``REF__PREFIX.variants.tsv`` tables of mixed
-    sites (coverage at least max(min_depth, 1)) after those — the run then takes the counts
-    route (``Workspace.run_with_tables``)."""
+    sites (coverage at least max(min_depth, 1)) after those, with ``depth`` the
+    ``REF__PREFIX.depth.tsv`` intervals of equal coverage, with ``lowcov`` the
+    ``REF__PREFIX.lowcov.tsv`` runs of coverage below max(min_depth, 1), and last, with
+    ``depth``, the one ``PREFIX.depth_summary.tsv`` — the run then takes the counts route
+    (``Workspace.run_with_tables``)."""
     import torch
 
     from .engine import _UPLOADERS, DeviceBatch, Workspace, needs_dense_layers, to_host
@@ -116,7 +130,8 @@ def consensus_batch(hb, thresholds, prefix, min_depth=1, fill=b"-", nchar=0, dev
 
     t = timings if timings is not None else {}
     t0 = time.perf_counter()
-    tables = bool(counts) or variants is not None
+    runs = bool(depth) or bool(lowcov)
+    tables = bool(counts) or variants is not None or runs
     db = DeviceBatch(hb, device, dense_layers=needs_dense_layers(fill, tables))
     t1 = time.perf_counter()
     ws = Workspace(db, thresholds, min_depth, fill, keep_counts=tables)
@@ -129,7 +144,12 @@ def consensus_batch(hb, thresholds, prefix, min_depth=1, fill=b"-", nchar=0, dev
     t0 = time.perf_counter()
     if tables:
         sites = (max(int(min_depth), 1),) + tuple(variants) if variants is not None else None
-        ctab, stab = ws.run_with_tables(counts=bool(counts), sites=sites)
+        least = max(int(min_depth), 1)
+        if runs:
+            ctab, stab, dtab, ltab = ws.run_with_tables(counts=bool(counts), sites=sites, depth=least if depth else None,
+                                                        lowcov=least if lowcov else None)
+        else:
+            ctab, stab = ws.run_with_tables(counts=bool(counts), sites=sites)
     else:
         ws.run()
     torch.cuda.synchronize(db.device)
@@ -144,11 +164,18 @@ def consensus_batch(hb, thresholds, prefix, min_depth=1, fill=b"-", nchar=0, dev
     for name, recs in fastas.items():
         files[name.encode("latin-1") + b"__" + pre + b".fasta"] = render(recs, nchar)
     if tables:   # (after build_records: a vote error raises and no file is returned)
-        from .table import SITES_HEADER, SITES_SUFFIX, table_files
+        from .table import (DEPTH_HEADER, DEPTH_SUFFIX, LOWCOV_HEADER, LOWCOV_SUFFIX, SITES_HEADER, SITES_SUFFIX,
+                            summary_file, table_files)
         if counts:
             files.update(table_files(hb, pre, ctab[0], to_host(ctab[1])))
         if variants is not None:
             files.update(table_files(hb, pre, stab[0], to_host(stab[1]), SITES_HEADER, SITES_SUFFIX))
+        if depth:
+            files.update(table_files(hb, pre, dtab[0], to_host(dtab[1]), DEPTH_HEADER, DEPTH_SUFFIX))
+        if lowcov:
+            files.update(table_files(hb, pre, ltab[0], to_host(ltab[1]), LOWCOV_HEADER, LOWCOV_SUFFIX))
+        if depth:   # (the host sums the tiles' statistics; it never reads the counts)
+            files.update(summary_file(hb, pre, dtab[2]))
     t["format"] = time.perf_counter() - t0
     return files
 
@@ -259,8 +286,8 @@ def consensus_batch_hip(sess, hb, thresholds, prefix, min_depth=1, fill=b"-", nc
 
 
 def _consensus_files_tables(filename, thresholds, prefix, min_depth, fill, nchar, maxdel_active, device, log,
-                            counts, variants):
-    """consensus_files with the count or variant tables: the torch engine path (consensus_batch)."""
+                            counts, variants, depth=False, lowcov=False):
+    """consensus_files with any of the tables: the torch engine path (consensus_batch)."""
     import torch
 
     from . import _lib
@@ -285,21 +312,23 @@ def _consensus_files_tables(filename, thresholds, prefix, min_depth, fill, nchar
     t["parse"] = time.perf_counter() - t0
     if log:
         _log_summary(log, hb.info)
-    files = consensus_batch(hb, thresholds, prefix, min_depth, fill, nchar, dev, t, counts=counts, variants=variants)
+    files = consensus_batch(hb, thresholds, prefix, min_depth, fill, nchar, dev, t, counts=counts, variants=variants,
+                            depth=depth, lowcov=lowcov)
     return RunResult(files, t, hb.info, hb.free_async())
 
 
 def consensus_files(filename, thresholds, prefix, min_depth=1, fill=b"-", nchar=0, maxdel_active=True,
-                    device=None, log=None, counts=False, variants=None):
+                    device=None, log=None, counts=False, variants=None, depth=False, lowcov=False):
     """Run the whole pipeline on one SAM/SAM.gz file; returns a RunResult whose
     ``files`` maps ``REF__PREFIX.fasta`` → content bytes (nothing written).  The device side
     runs through the HIP runtime directly (hiprun.py): this path never imports PyTorch.
     With ``counts`` the files also hold the ``REF__PREFIX.counts.tsv`` count tables, with
     ``variants`` = (min_alt, min_frac) the ``REF__PREFIX.variants.tsv`` tables of mixed sites,
-    and the run goes through the torch engine path instead (``consensus_batch``)."""
-    if counts or variants is not None:
+    with ``depth`` / ``lowcov`` the ``.depth.tsv`` / ``.lowcov.tsv`` runs of coverage (and the
+    depth summary), and the run goes through the torch engine path instead (``consensus_batch``)."""
+    if counts or variants is not None or depth or lowcov:
         return _consensus_files_tables(filename, thresholds, prefix, min_depth, fill, nchar, maxdel_active, device, log,
-                                       bool(counts), variants)
+                                       bool(counts), variants, bool(depth), bool(lowcov))
     from .batch import Parser
     from .hiprun import Session, device_index
 
@@ -331,12 +360,13 @@ def consensus_files(filename, thresholds, prefix, min_depth=1, fill=b"-", nchar=
     return RunResult(files, t, hb.info, hb.free_async())
 
 
-def run_text(sam_text, argv, device=None, counts=False, variants=None):
+def run_text(sam_text, argv, device=None, counts=False, variants=None, depth=False, lowcov=False):
     """Library entry for tests: SAM text + CLI args (without -i) → (status, {fname: str}).
     status is "ok" or the reference's exception class name; nothing touches the disk.
     ``counts`` (or ``--counts`` among the args): the count tables too; ``variants`` =
     (min_alt, min_frac) (or ``--variants`` and its options among the args): the tables of
-    mixed sites too."""
+    mixed sites too; ``depth`` / ``lowcov`` (or ``--depth`` / ``--lowcov``): the depth intervals
+    with their summary / the low-coverage runs too."""
     from .batch import parse_text
 
     parser = build_parser()
@@ -348,7 +378,7 @@ def run_text(sam_text, argv, device=None, counts=False, variants=None):
         hb = parse_text(sam_text, not isinstance(args.maxdel, str), 150)
         files = consensus_batch(hb, thresholds, os.fsencode(prefix), args.min_depth,
                                 os.fsencode(args.fill), args.n, device, counts=bool(counts or args.counts),
-                                variants=variants)
+                                variants=variants, depth=bool(depth or args.depth), lowcov=bool(lowcov or args.lowcov))
     except (KeyError, IndexError, ValueError, ZeroDivisionError, OverflowError) as e:
         return type(e).__name__, {}
     return "ok", {k.decode("latin-1"): v.decode("latin-1") for k, v in files.items()}
@@ -418,7 +448,8 @@ def main(argv=None):
     parser = build_parser()
     args = parser.parse_args(argv)
     variants = variants_of(parser, args)
-    for flag, on in (("--counts", args.counts), ("--variants", variants is not None)):
+    for flag, on in (("--counts", args.counts), ("--variants", variants is not None), ("--depth", args.depth),
+                     ("--lowcov", args.lowcov)):
         if on:   # (refused before a folder is made or a device touched)
             if _dist_env()[0] > 1:
                 parser.error(flag + " is not available with more than one process (WORLD_SIZE > 1)")
@@ -454,7 +485,7 @@ def main(argv=None):
         else:
             res = consensus_files(filename, thresholds, os.fsencode(prefix), args.min_depth,
                                   os.fsencode(args.fill), args.n, maxdel_active, log=lambda s: print(s),
-                                  counts=args.counts, variants=variants)
+                                  counts=args.counts, variants=variants, depth=args.depth, lowcov=args.lowcov)
             files = res.files
     tables = []
     for fname, body in files.items():                                             # :411-424
@@ -462,7 +493,13 @@ def main(argv=None):
         with open(path, "wb") as fh:
             fh.write(body)
         shown = os.fsdecode(path)
-        if args.counts and fname.endswith(b".counts.tsv"):
+        if args.depth and fname.endswith(b".depth_summary.tsv"):   # (PREFIX alone: no reference)
+            tables.append("Depth summary saved in: " + shown)
+        elif args.depth and fname.endswith(b".depth.tsv"):         # (the run tables come after the others, in this order)
+            tables.append("Depth table saved for " + os.fsdecode(fname[: fname.rfind(b"__")]) + " in: " + shown)
+        elif args.lowcov and fname.endswith(b".lowcov.tsv"):
+            tables.append("Low-coverage table saved for " + os.fsdecode(fname[: fname.rfind(b"__")]) + " in: " + shown)
+        elif args.counts and fname.endswith(b".counts.tsv"):
             tables.append("Count table saved for " + os.fsdecode(fname[: fname.rfind(b"__")]) + " in: " + shown)
         elif variants is not None and fname.endswith(b".variants.tsv"):   # (the files come after the count tables)
             tables.append("Variant table saved for " + os.fsdecode(fname[: fname.rfind(b"__")]) + " in: " + shown)

@@ -1,4 +1,5 @@
-// s2c_text.h — what the kernels that format counts as text share (s2c_table.hip, s2c_sites.hip):
+// s2c_text.h — what the kernels that format counts as text share (s2c_table.hip, s2c_sites.hip,
+// s2c_runs.hip):
 // the decimal digit code, one position's row and its counts line, the workgroup's scan of line
 // lengths to offsets, the blocks {a, b, p0} with their guards, and the aligned store of a
 // sub-block's text out of its LDS image.

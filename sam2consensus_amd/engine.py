@@ -423,24 +423,83 @@ class Workspace:
                                     _ptr(text), total, st))
         return offs, text[:total]
 
-    def run_with_tables(self, counts=True, sites=None):
-        """``run()`` through the counts route, with either or both tables: every tile's counts
+    def _table_refs(self):
+        """Device int64 [n_tiles][2] {s, e}: the global range of the reference each tile lies in
+        (``_table_blocks``' companion for the run tables)."""
+        if getattr(self, "_trefs", None) is None:
+            hb = self.db.hb
+            ref = hb.tiles[:, 2].astype(np.int64)
+            refs = np.empty((len(ref), 2), dtype=np.int64)
+            refs[:, 0] = np.asarray(hb.ref_off, dtype=np.int64)[ref]
+            refs[:, 1] = refs[:, 0] + np.asarray(hb.ref_len, dtype=np.int64)[ref]
+            self._trefs = _up(refs.reshape(-1), self.db.device)
+        return self._trefs
+
+    def depth_table(self, cut=0, min_cov=1):
+        """The filled ``counts`` as the text of the runs of equal coverage (table.py;
+        s2c_runs_mark into a bit per run start, then s2c_runs_len, the prefix sum and
+        s2c_runs_write, on the current stream).  ``cut`` = 0: the depth lines of every run;
+        ``cut`` >= 1: the lines of the runs of coverage < cut (the low-coverage mask).  Returns
+        (offs, device text, stats): the first two as ``counts_table``'s, with its preconditions
+        — the lines of the runs that start in tile k at [offs[k], offs[k+1]); ``stats`` int64
+        numpy [n_tiles][6] {runs, covered, passed, sumcov, mincov, maxcov} of those runs
+        (``passed``: coverage >= min_cov), or None when cut >= 1."""
+        if not self.keep_counts or self.tile_range is not None:
+            raise ValueError("depth_table needs Workspace(keep_counts=True) over the whole batch")
+        if not self._counts_filled:
+            raise ValueError("depth_table needs filled counts (accumulate / pileup_counts; s2c_consensus zeroes them)")
+        cut, min_cov = int(cut), int(min_cov)
+        if cut < 0 or min_cov < 0:
+            raise ValueError("depth_table: cut >= 0 and min_cov >= 0")
+        i = self.db.info
+        dev = self.db.device
+        nt = int(i.n_tiles)
+        if nt == 0:
+            return (np.zeros(1, dtype=np.int64), torch.empty(0, dtype=torch.uint8, device=dev),
+                    None if cut else np.zeros((0, 6), dtype=np.int64))
+        st = self.stream_handle()
+        blocks, refs = self._table_blocks(), self._table_refs()
+        mask = torch.empty(max((int(i.padded_len) + 63) // 64, 1), dtype=torch.int64, device=dev)
+        offs_d = torch.zeros(nt + 1, dtype=torch.int64, device=dev)
+        lens = torch.empty(nt, dtype=torch.int64, device=dev)
+        stats = None if cut else torch.empty(nt * 6, dtype=torch.int64, device=dev)
+        L.check(lib.s2c_runs_mark(_ptr(self.counts), i.padded_len, cut, _ptr(mask), st))
+        L.check(lib.s2c_runs_len(_ptr(self.counts), i.padded_len, _ptr(mask), _ptr(blocks), _ptr(refs), nt, cut, min_cov,
+                                 _ptr(lens), _ptr(stats) if stats is not None else None, st))
+        torch.cumsum(lens, 0, out=offs_d[1:])
+        offs = offs_d.cpu().numpy()
+        total = int(offs[-1])
+        text = torch.empty(max(total, 16), dtype=torch.uint8, device=dev)
+        L.check(lib.s2c_runs_write(_ptr(self.counts), i.padded_len, _ptr(mask), _ptr(blocks), _ptr(refs), _ptr(offs_d), nt,
+                                   cut, _ptr(text), total, st))
+        return offs, text[:total], (stats.cpu().numpy().reshape(nt, 6) if stats is not None else None)
+
+    def run_with_tables(self, counts=True, sites=None, *, depth=None, lowcov=None):
+        """``run()`` through the counts route, with any of the tables: every tile's counts
         stored (s2c_accumulate on zeroed counts, the insertion tables kept), formatted as text
         (before the vote, which leaves the counts zero), then every tile voted from them
         (``vote_all``); ``fetch()`` yields the FASTA results as after ``run()``.  ``counts``:
         the count tables; ``sites`` (min_cov, min_alt, min_frac): the tables of mixed sites.
         Returns (counts_table() or None, sites_table(*sites) or None): a table not asked for
-        is not formatted."""
+        is not formatted.  With ``depth`` = min_cov (the depth intervals, ``passed`` counted at
+        min_cov) or ``lowcov`` = cut (the runs of coverage < cut), two more:
+        (..., depth_table(0, depth) or None, depth_table(lowcov) or None)."""
         if not self.keep_counts:
             raise ValueError("run_with_tables needs Workspace(keep_counts=True)")
+        if lowcov is not None and int(lowcov) < 1:
+            raise ValueError("run_with_tables: lowcov is the least coverage that passes, >= 1")
         self._counts_ready()
         # (set first: if a stage raises, a reused workspace zeroes its counts before its next run)
         self._counts_filled = True
         self.accumulate(keep_tables=True)
         table = self.counts_table() if counts else None
         stable = self.sites_table(*sites) if sites is not None else None
+        dtable = self.depth_table(0, depth) if depth is not None else None
+        ltable = self.depth_table(lowcov) if lowcov is not None else None
         self.vote_all()
-        return table, stable
+        if depth is None and lowcov is None:
+            return table, stable
+        return table, stable, dtable, ltable
 
     def run_with_counts(self):
         """``run_with_tables`` with the count tables alone.  Returns counts_table()'s (offs,

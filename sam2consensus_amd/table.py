@@ -17,6 +17,17 @@ symbol, the other symbols with a non-zero count in rank order, ``dddd = alt * 10
 All six symbols take part, ``-`` and ``N`` included, as in the vote; insertion columns do not.
 The device selects and formats (csrc/s2c_sites.hip, ``Workspace.sites_table``); ``site_mask``
 and ``format_sites`` are the model.
+
+Depth intervals (``--depth``): ``REF__PREFIX.depth.tsv``, one line ``start\tend\tcov`` per
+maximal run of equal coverage (the sum of the six counts), zero-coverage runs included,
+positions 1-based and inclusive: the runs partition [1, LN].  One ``PREFIX.depth_summary.tsv``
+per run of the program holds a line per reference: its length, the positions with coverage
+>= 1 and >= max(-m, 1), the sum, least and largest coverage and the number of runs.  The
+low-coverage mask (``--lowcov``): ``REF__PREFIX.lowcov.tsv``, one line ``start\tend`` per
+maximal run of positions with coverage < max(-m, 1) — where the vote wrote the fill character
+(sam2consensus.py:358).  The device finds and formats the runs (csrc/s2c_runs.hip,
+``Workspace.depth_table``); ``depth_runs``, ``format_depth``, ``format_lowcov`` and
+``depth_stats`` are the model.
 """
 from __future__ import annotations
 
@@ -27,6 +38,13 @@ SUFFIX = b".counts.tsv"
 SITES_HEADER = b"pos\tcov\t-\tA\tC\tG\tN\tT\tmajor\talt\taf\n"
 SITES_SUFFIX = b".variants.tsv"
 SYMBOLS = "-ACGNT"
+DEPTH_HEADER = b"start\tend\tcov\n"
+DEPTH_SUFFIX = b".depth.tsv"
+LOWCOV_HEADER = b"start\tend\n"
+LOWCOV_SUFFIX = b".lowcov.tsv"
+SUMMARY_HEADER = b"ref\tlen\tcovered\tpassed\tsumcov\tmincov\tmaxcov\truns\n"
+SUMMARY_SUFFIX = b".depth_summary.tsv"
+EMPTY_STATS = (0, 0, 0, 0, 2 ** 63 - 1, -1)   # a block without a run start (s2c_runs_len)
 
 
 def format_rows(counts_6xL, p0=1):
@@ -89,3 +107,61 @@ def table_files(hb, prefix, offs, body, header=HEADER, suffix=SUFFIX):
         a, b = int(offs[f0]), int(offs[f0 + n])
         files[hb.names[r].encode("latin-1") + b"__" + pre + suffix] = header + body[a:b]
     return files
+
+
+def coverage(counts_6xL):
+    """The coverage of every position of counts[6][L] as Python ints (it may pass 2^32)."""
+    c = _c6(counts_6xL)
+    return c.astype(np.int64).sum(axis=0).tolist() if c.shape[1] else []
+
+
+def depth_runs(cov):
+    """The maximal runs of equal value in ``cov``: (start, end, value) triples, ``start`` the
+    0-based first index and ``end`` the index after the last; they partition [0, len(cov))."""
+    runs, start = [], 0
+    for j in range(1, len(cov) + 1):
+        if j == len(cov) or cov[j] != cov[start]:
+            runs.append((start, j, cov[start]))
+            start = j
+    return runs
+
+
+def format_depth(counts_6xL, p0=1):
+    """The depth lines (no header) of counts[6][L], position ``p0`` printed for column 0."""
+    return "".join("%d\t%d\t%d\n" % (int(p0) + s, int(p0) + e - 1, v)
+                   for s, e, v in depth_runs(coverage(counts_6xL))).encode("ascii")
+
+
+def format_lowcov(counts_6xL, p0=1, min_cov=1):
+    """The low-coverage lines (no header) of counts[6][L]: the runs of coverage < ``min_cov``."""
+    low = [v < int(min_cov) for v in coverage(counts_6xL)]
+    return "".join("%d\t%d\n" % (int(p0) + s, int(p0) + e - 1) for s, e, v in depth_runs(low) if v).encode("ascii")
+
+
+def depth_stats(counts_6xL, min_cov):
+    """(runs, covered, passed, sumcov, mincov, maxcov) of counts[6][L], as s2c_runs_len's
+    stats: the depth lines, the positions with coverage >= 1 and >= ``min_cov``, the sum, least
+    and largest coverage; ``EMPTY_STATS`` for L = 0."""
+    cov = coverage(counts_6xL)
+    if not cov:
+        return EMPTY_STATS
+    return (len(depth_runs(cov)), sum(v >= 1 for v in cov), sum(v >= int(min_cov) for v in cov), sum(cov),
+            min(cov), max(cov))
+
+
+def summary_file(hb, prefix, stats):
+    """{``PREFIX.depth_summary.tsv``: bytes} from ``Workspace.depth_table``'s per-tile
+    ``stats[n_tiles][6]``: one line per reference with a depth table (``table_files``' rule),
+    in reference order, its tiles' statistics summed (the least and largest coverage: the
+    least and largest)."""
+    pre = prefix.encode("latin-1") if isinstance(prefix, str) else prefix
+    lines = [SUMMARY_HEADER]
+    for r in range(hb.info.n_refs):
+        if hb.ref_reads[r] == 0:
+            continue
+        f0, n = int(hb.ref_first_block[r]), int(hb.ref_nblocks[r])
+        st = [[int(v) for v in row] for row in stats[f0:f0 + n]] or [list(EMPTY_STATS)]
+        runs, covered, passed, sumcov = (sum(row[k] for row in st) for k in range(4))
+        fields = (int(hb.ref_len[r]), covered, passed, sumcov, min(row[4] for row in st), max(row[5] for row in st), runs)
+        lines.append(hb.names[r].encode("latin-1") + b"\t" + "\t".join(str(v) for v in fields).encode("ascii") + b"\n")
+    return {pre + SUMMARY_SUFFIX: b"".join(lines)}
