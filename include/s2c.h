@@ -30,7 +30,10 @@
  *          (3) k_reads: the insertion events (:73-75, :221) hashed by (position, motif)
  *              into per-tile open-addressing tables with per-entry counts (:262-271), and
  *              the run records of the rare long pieces;
- *          (4) k_consensus: tiles whose depth or insertion layout exceeds one workgroup.
+ *          (4) k_consensus: tiles whose depth or insertion layout exceeds one workgroup;
+ *          (5) the tables as text, formatted where the counts and the insertion events are:
+ *              k_table_* (--counts), k_sites_* (--variants), k_runs_* (--depth, --lowcov) and
+ *              k_ins_* (--insertions: the motifs of (3) grouped, ordered and printed per tile).
  */
 #ifndef S2C_H
 #define S2C_H
@@ -595,6 +598,45 @@ int s2c_runs_len(const uint32_t *counts, int64_t padded_len, const uint64_t *mas
 int s2c_runs_write(const uint32_t *counts, int64_t padded_len, const uint64_t *mask, const int64_t *blocks,
                    const int64_t *refs, const int64_t *offs, int64_t n, int64_t cut, uint8_t *dst, int64_t dst_len,
                    void *stream);
+
+/* Insertion motif tables as text (the CLI's --insertions; csrc/s2c_ins.hip), from what
+ * s2c_accumulate(d, 1, ...) leaves and s2c_consensus then clears: per tile the hash table of
+ * the short motifs (s2c_dev.ibkt: {key lo, key hi, count, 0}, key = pos | len << 11 | 3-bit
+ * codes << (16 + 3c), pos relative to the tile, codes in S2C_NSYM order) and the long-motif
+ * events (ilong: {pos, len, q lo, q hi}, the first ilong_n[t] of the tile's lcap, clamped to
+ * it; the motif is query bases [q, q + len) of the planes bq / bx of n_qwords words), with any
+ * counts[6][padded_len] and the count tables' blocks {a, b, p0}: block i goes with tile i
+ * (a = the tile's first position; b == a lists nothing).  Every pointer is a device pointer, so
+ * a test can pass tables it built itself; tiles = [n_tiles][S2C_TILE_WORDS], of which words
+ * 4-7 {boff, bcap, loff, lcap} are read, n_bkt / n_lng the slots of ibkt / ilong (both below
+ * 2^32).  One line per distinct (position, motif) with reads >= min_reads (>= 1), equal long
+ * events counted together first: "P\tCOV\tREADS\tLEN\tMOTIF\n", P = p0 + pos, COV the 64-bit
+ * sum of the six counts at a + pos, plain decimal, MOTIF in the characters -ACGNT.  A tile's
+ * lines are ordered by pos rising, then READS falling, LEN rising, MOTIF symbol by symbol in
+ * S2C_NSYM order — a total order: the bytes do not depend on hash slots or on the order the
+ * events arrived in.  Slots and events that are no entry are not listed: a zero key or count,
+ * a short length outside [1, S2C_SHORT_MOTIF], a long length outside [1, 2^24), pos >= b - a,
+ * bases outside the planes.
+ *   scratch: 32 bytes per slot of ibkt and ilong, 32 * (n_bkt + n_lng) in all, 16-byte aligned
+ *   and at least 16 bytes: two arrays of n_bkt + n_lng 16-byte records (the entries bucketed by
+ *   position; their places in order with each line's offset), tile t's at boff + loff, bcap +
+ *   lcap of them — the offsets are running sums, so the tiles' parts are disjoint.  s2c_ins_len
+ *   fills it and s2c_ins_write reads it: the same tiles, sizes and scratch go to both.
+ * s2c_ins_len writes lens[i], the exact bytes of tile i's lines; the caller forms offs[n + 1];
+ * s2c_ins_write writes tile i's lines to dst[offs[i], offs[i+1]) and no byte outside it.  A
+ * block outside the count tables' bounds gets lens[i] = 0, as does a tile record reaching past
+ * n_bkt or n_lng; s2c_ins_write skips those and a block with offs[i] < 0, offs[i+1] < offs[i]
+ * or offs[i+1] > dst_len.  Every loop is bounded by bcap, lcap or a checked length.  Both calls
+ * are asynchronous on stream and allocate nothing; they leave ibkt, ilong, ilong_n and counts
+ * as they are and add no struct field (ABI 14 stands). */
+int s2c_ins_len(const uint32_t *tiles, int64_t n_tiles, const uint32_t *ibkt, int64_t n_bkt, const uint32_t *ilong,
+                int64_t n_lng, const uint32_t *ilong_n, const uint32_t *bq, const uint32_t *bx, int64_t n_qwords,
+                const uint32_t *counts, int64_t padded_len, const int64_t *blocks, int64_t min_reads,
+                uint32_t *scratch, int64_t *lens, void *stream);
+int s2c_ins_write(const uint32_t *tiles, int64_t n_tiles, int64_t n_bkt, int64_t n_lng, const uint32_t *bq,
+                  const uint32_t *bx, int64_t n_qwords, const uint32_t *counts, int64_t padded_len,
+                  const int64_t *blocks, const uint32_t *scratch, const int64_t *offs, uint8_t *dst, int64_t dst_len,
+                  void *stream);
 
 /* Diagnostics (tests only, not part of the product path): k_reads over every piece, then
  * every tile's counts stored to d->counts ([6][padded_len] u32) and no vote. */

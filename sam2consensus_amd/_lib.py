@@ -122,6 +122,7 @@ EXPORTS = [
     "s2c_gather_bodies_dev", "s2c_plan_set_cus", "s2c_table_len", "s2c_table_write",
     "s2c_sites_mark", "s2c_sites_len", "s2c_sites_write",
     "s2c_runs_mark", "s2c_runs_len", "s2c_runs_write",
+    "s2c_ins_len", "s2c_ins_write",
 ]
 
 
@@ -207,6 +208,10 @@ def _load():
         "s2c_runs_mark": (C.c_int, [_VP, C.c_int64, C.c_int64, _VP, _VP]),
         "s2c_runs_len": (C.c_int, [_VP, C.c_int64, _VP, _VP, _VP, C.c_int64, C.c_int64, C.c_int64, _VP, _VP, _VP]),
         "s2c_runs_write": (C.c_int, [_VP, C.c_int64, _VP, _VP, _VP, _VP, C.c_int64, C.c_int64, _VP, C.c_int64, _VP]),
+        "s2c_ins_len": (C.c_int, [_VP, C.c_int64, _VP, C.c_int64, _VP, C.c_int64, _VP, _VP, _VP, C.c_int64, _VP, C.c_int64, _VP,
+                                  C.c_int64, _VP, _VP, _VP]),
+        "s2c_ins_write": (C.c_int, [_VP, C.c_int64, C.c_int64, C.c_int64, _VP, _VP, C.c_int64, _VP, C.c_int64, _VP, _VP, _VP, _VP,
+                                    C.c_int64, _VP]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)

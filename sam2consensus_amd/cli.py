@@ -69,6 +69,15 @@ def build_parser():
                    help="Also write REF__PREFIX.lowcov.tsv beside each FASTA file: one line start, end per "
                         "maximal run of positions with coverage below max(-m, 1), where the consensus holds "
                         "the -f character. Not available with more than one process or with S2C_STREAM")
+    p.add_argument("--insertions", action="store_true", dest="insertions", default=False,
+                   help="Also write REF__PREFIX.insertions.tsv beside each FASTA file: one line pos, cov, reads, len, "
+                        "motif (tab-separated) per distinct insertion motif at a position: the 1-based position whose "
+                        "consensus letter the inserted columns follow, the coverage there, the reads carrying exactly "
+                        "this motif, its length and its characters; ordered by position, then reads (falling), "
+                        "length and motif; independent of -c, -m, -f, -n and -d. "
+                        "Not available with more than one process or with S2C_STREAM")
+    p.add_argument("--min-ins-reads", action="store", dest="min_ins_reads", type=int, default=None, metavar="N",
+                   help="With --insertions: list a motif only when at least N reads carry it, default=1")
     p.add_argument("--min-alt-reads", action="store", dest="min_alt_reads", type=int, default=None, metavar="N",
                    help="With --variants: least number of reads not of the major symbol at a site, default=2")
     p.add_argument("--min-alt-frac", action="store", dest="min_alt_frac", type=float, default=None, metavar="F",
@@ -98,6 +107,23 @@ def variants_of(parser, args):
     return n, f
 
 
+MIN_INS_READS = 1
+
+
+def insertions_of(parser, args):
+    """min_reads of --insertions or None; --min-ins-reads below 1 or without --insertions is
+    the parser's error (exit status 2)."""
+    n = args.min_ins_reads
+    if not args.insertions:
+        if n is not None:
+            parser.error("--min-ins-reads needs --insertions")
+        return None
+    n = MIN_INS_READS if n is None else n
+    if not 1 <= n < 2 ** 32:
+        parser.error("--min-ins-reads must be at least 1")
+    return n
+
+
 class RunResult:
     def __init__(self, files, timings, info, pending=None):
         self.files = files          # {filename: bytes}
@@ -114,15 +140,16 @@ class RunResult:
 
 
 def consensus_batch(hb, thresholds, prefix, min_depth=1, fill=b"-", nchar=0, device=None, timings=None,
-                    counts=False, variants=None, depth=False, lowcov=False):
+                    counts=False, variants=None, depth=False, lowcov=False, insertions=None):
     """Device pipeline on a parsed HostBatch → {``REF__PREFIX.fasta``: bytes}; with ``counts``
     also the ``REF__PREFIX.counts.tsv`` count tables (table.py), after the FASTA entries, and
     with ``variants`` = (min_alt, min_frac) the ``REF__PREFIX.variants.tsv`` tables of mixed
     sites (coverage at least max(min_depth, 1)) after those, with ``depth`` the
     ``REF__PREFIX.depth.tsv`` intervals of equal coverage, with ``lowcov`` the
     ``REF__PREFIX.lowcov.tsv`` runs of coverage below max(min_depth, 1), and last, with
-    ``depth``, the one ``PREFIX.depth_summary.tsv`` — the run then takes the counts route
-    (``Workspace.run_with_tables``)."""
+    ``depth``, the one ``PREFIX.depth_summary.tsv``; with ``insertions`` = min_reads the
+    ``REF__PREFIX.insertions.tsv`` insertion motif tables after all of those — the run then
+    takes the counts route (``Workspace.run_with_tables``)."""
     import torch
 
     from .engine import _UPLOADERS, DeviceBatch, Workspace, needs_dense_layers, to_host
@@ -131,7 +158,7 @@ def consensus_batch(hb, thresholds, prefix, min_depth=1, fill=b"-", nchar=0, dev
     t = timings if timings is not None else {}
     t0 = time.perf_counter()
     runs = bool(depth) or bool(lowcov)
-    tables = bool(counts) or variants is not None or runs
+    tables = bool(counts) or variants is not None or runs or insertions is not None
     db = DeviceBatch(hb, device, dense_layers=needs_dense_layers(fill, tables))
     t1 = time.perf_counter()
     ws = Workspace(db, thresholds, min_depth, fill, keep_counts=tables)
@@ -145,11 +172,12 @@ def consensus_batch(hb, thresholds, prefix, min_depth=1, fill=b"-", nchar=0, dev
     if tables:
         sites = (max(int(min_depth), 1),) + tuple(variants) if variants is not None else None
         least = max(int(min_depth), 1)
+        res = ws.run_with_tables(counts=bool(counts), sites=sites, depth=least if depth else None,
+                                 lowcov=least if lowcov else None, insertions=insertions)
+        itab = res[-1] if insertions is not None else None
+        ctab, stab = res[:2]
         if runs:
-            ctab, stab, dtab, ltab = ws.run_with_tables(counts=bool(counts), sites=sites, depth=least if depth else None,
-                                                        lowcov=least if lowcov else None)
-        else:
-            ctab, stab = ws.run_with_tables(counts=bool(counts), sites=sites)
+            dtab, ltab = res[2:4]
     else:
         ws.run()
     torch.cuda.synchronize(db.device)
@@ -164,8 +192,8 @@ def consensus_batch(hb, thresholds, prefix, min_depth=1, fill=b"-", nchar=0, dev
     for name, recs in fastas.items():
         files[name.encode("latin-1") + b"__" + pre + b".fasta"] = render(recs, nchar)
     if tables:   # (after build_records: a vote error raises and no file is returned)
-        from .table import (DEPTH_HEADER, DEPTH_SUFFIX, LOWCOV_HEADER, LOWCOV_SUFFIX, SITES_HEADER, SITES_SUFFIX,
-                            summary_file, table_files)
+        from .table import (DEPTH_HEADER, DEPTH_SUFFIX, INS_HEADER, INS_SUFFIX, LOWCOV_HEADER, LOWCOV_SUFFIX, SITES_HEADER,
+                            SITES_SUFFIX, summary_file, table_files)
         if counts:
             files.update(table_files(hb, pre, ctab[0], to_host(ctab[1])))
         if variants is not None:
@@ -176,6 +204,8 @@ def consensus_batch(hb, thresholds, prefix, min_depth=1, fill=b"-", nchar=0, dev
             files.update(table_files(hb, pre, ltab[0], to_host(ltab[1]), LOWCOV_HEADER, LOWCOV_SUFFIX))
         if depth:   # (the host sums the tiles' statistics; it never reads the counts)
             files.update(summary_file(hb, pre, dtab[2]))
+        if insertions is not None:
+            files.update(table_files(hb, pre, itab[0], to_host(itab[1]), INS_HEADER, INS_SUFFIX))
     t["format"] = time.perf_counter() - t0
     return files
 
@@ -286,7 +316,7 @@ def consensus_batch_hip(sess, hb, thresholds, prefix, min_depth=1, fill=b"-", nc
 
 
 def _consensus_files_tables(filename, thresholds, prefix, min_depth, fill, nchar, maxdel_active, device, log,
-                            counts, variants, depth=False, lowcov=False):
+                            counts, variants, depth=False, lowcov=False, insertions=None):
     """consensus_files with any of the tables: the torch engine path (consensus_batch)."""
     import torch
 
@@ -313,22 +343,23 @@ def _consensus_files_tables(filename, thresholds, prefix, min_depth, fill, nchar
     if log:
         _log_summary(log, hb.info)
     files = consensus_batch(hb, thresholds, prefix, min_depth, fill, nchar, dev, t, counts=counts, variants=variants,
-                            depth=depth, lowcov=lowcov)
+                            depth=depth, lowcov=lowcov, insertions=insertions)
     return RunResult(files, t, hb.info, hb.free_async())
 
 
 def consensus_files(filename, thresholds, prefix, min_depth=1, fill=b"-", nchar=0, maxdel_active=True,
-                    device=None, log=None, counts=False, variants=None, depth=False, lowcov=False):
+                    device=None, log=None, counts=False, variants=None, depth=False, lowcov=False, insertions=None):
     """Run the whole pipeline on one SAM/SAM.gz file; returns a RunResult whose
     ``files`` maps ``REF__PREFIX.fasta`` → content bytes (nothing written).  The device side
     runs through the HIP runtime directly (hiprun.py): this path never imports PyTorch.
     With ``counts`` the files also hold the ``REF__PREFIX.counts.tsv`` count tables, with
     ``variants`` = (min_alt, min_frac) the ``REF__PREFIX.variants.tsv`` tables of mixed sites,
     with ``depth`` / ``lowcov`` the ``.depth.tsv`` / ``.lowcov.tsv`` runs of coverage (and the
-    depth summary), and the run goes through the torch engine path instead (``consensus_batch``)."""
-    if counts or variants is not None or depth or lowcov:
+    depth summary), with ``insertions`` = min_reads the ``.insertions.tsv`` insertion motif tables,
+    and the run goes through the torch engine path instead (``consensus_batch``)."""
+    if counts or variants is not None or depth or lowcov or insertions is not None:
         return _consensus_files_tables(filename, thresholds, prefix, min_depth, fill, nchar, maxdel_active, device, log,
-                                       bool(counts), variants, bool(depth), bool(lowcov))
+                                       bool(counts), variants, bool(depth), bool(lowcov), insertions)
     from .batch import Parser
     from .hiprun import Session, device_index
 
@@ -360,25 +391,28 @@ def consensus_files(filename, thresholds, prefix, min_depth=1, fill=b"-", nchar=
     return RunResult(files, t, hb.info, hb.free_async())
 
 
-def run_text(sam_text, argv, device=None, counts=False, variants=None, depth=False, lowcov=False):
+def run_text(sam_text, argv, device=None, counts=False, variants=None, depth=False, lowcov=False, insertions=None):
     """Library entry for tests: SAM text + CLI args (without -i) → (status, {fname: str}).
     status is "ok" or the reference's exception class name; nothing touches the disk.
     ``counts`` (or ``--counts`` among the args): the count tables too; ``variants`` =
     (min_alt, min_frac) (or ``--variants`` and its options among the args): the tables of
     mixed sites too; ``depth`` / ``lowcov`` (or ``--depth`` / ``--lowcov``): the depth intervals
-    with their summary / the low-coverage runs too."""
+    with their summary / the low-coverage runs too; ``insertions`` = min_reads (or ``--insertions``
+    and ``--min-ins-reads``): the insertion motif tables too."""
     from .batch import parse_text
 
     parser = build_parser()
     args = parser.parse_args(["-i", "in.sam"] + list(argv))
     variants = variants_of(parser, args) or variants
+    insertions = insertions_of(parser, args) or insertions
     try:
         thresholds = [float(i) for i in args.thresholds.split(",")]
         prefix = args.prefix or "in"
         hb = parse_text(sam_text, not isinstance(args.maxdel, str), 150)
         files = consensus_batch(hb, thresholds, os.fsencode(prefix), args.min_depth,
                                 os.fsencode(args.fill), args.n, device, counts=bool(counts or args.counts),
-                                variants=variants, depth=bool(depth or args.depth), lowcov=bool(lowcov or args.lowcov))
+                                variants=variants, depth=bool(depth or args.depth), lowcov=bool(lowcov or args.lowcov),
+                                insertions=insertions)
     except (KeyError, IndexError, ValueError, ZeroDivisionError, OverflowError) as e:
         return type(e).__name__, {}
     return "ok", {k.decode("latin-1"): v.decode("latin-1") for k, v in files.items()}
@@ -448,8 +482,9 @@ def main(argv=None):
     parser = build_parser()
     args = parser.parse_args(argv)
     variants = variants_of(parser, args)
+    insertions = insertions_of(parser, args)
     for flag, on in (("--counts", args.counts), ("--variants", variants is not None), ("--depth", args.depth),
-                     ("--lowcov", args.lowcov)):
+                     ("--lowcov", args.lowcov), ("--insertions", insertions is not None)):
         if on:   # (refused before a folder is made or a device touched)
             if _dist_env()[0] > 1:
                 parser.error(flag + " is not available with more than one process (WORLD_SIZE > 1)")
@@ -485,7 +520,8 @@ def main(argv=None):
         else:
             res = consensus_files(filename, thresholds, os.fsencode(prefix), args.min_depth,
                                   os.fsencode(args.fill), args.n, maxdel_active, log=lambda s: print(s),
-                                  counts=args.counts, variants=variants, depth=args.depth, lowcov=args.lowcov)
+                                  counts=args.counts, variants=variants, depth=args.depth, lowcov=args.lowcov,
+                                  insertions=insertions)
             files = res.files
     tables = []
     for fname, body in files.items():                                             # :411-424
@@ -497,6 +533,8 @@ def main(argv=None):
             tables.append("Depth summary saved in: " + shown)
         elif args.depth and fname.endswith(b".depth.tsv"):         # (the run tables come after the others, in this order)
             tables.append("Depth table saved for " + os.fsdecode(fname[: fname.rfind(b"__")]) + " in: " + shown)
+        elif insertions is not None and fname.endswith(b".insertions.tsv"):   # (last: after the depth summary)
+            tables.append("Insertion table saved for " + os.fsdecode(fname[: fname.rfind(b"__")]) + " in: " + shown)
         elif args.lowcov and fname.endswith(b".lowcov.tsv"):
             tables.append("Low-coverage table saved for " + os.fsdecode(fname[: fname.rfind(b"__")]) + " in: " + shown)
         elif args.counts and fname.endswith(b".counts.tsv"):

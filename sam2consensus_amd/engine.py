@@ -249,6 +249,7 @@ class Workspace:
         else:   # (zero before the first run; s2c_consensus leaves it zero: s2c_dev.counts)
             self.counts = z8(6 * i.padded_len * 4 if keep_counts else sz.counts)
         self._counts_filled = False   # s2c_pileup_counts leaves counts filled: zeroed before a run
+        self._tables_held = False     # the batch's insertion tables are in ibkt / ilong (accumulate(keep_tables=True))
         self.ins_cols = u8(sz.ins_cols)
         self.ins_chr = u8(sz.ins_chr)
         self.blk_len = u8(sz.blk_len)
@@ -301,11 +302,13 @@ class Workspace:
         L.check(lib.s2c_pileup(C.byref(self.dev), self.stream_handle()))
 
     def consensus(self):
+        self._tables_held = False   # (k_consensus clears the deep tiles' insertion tables)
         L.check(lib.s2c_consensus(C.byref(self.dev), self.stream_handle()))
 
     def run(self):
         """reads → pileup (+ insertion columns, vote, FASTA bodies) → deep tiles (no host sync)."""
         self._counts_ready()
+        self._tables_held = False
         L.check(lib.s2c_run(C.byref(self.dev), self.stream_handle()))
 
     def record_done(self):
@@ -337,12 +340,15 @@ class Workspace:
     # ---- results
     def accumulate(self, keep_tables=False):
         """Streamed batch of unsorted input: this batch's counts added to ``counts``."""
+        self._tables_held = False
         L.check(lib.s2c_accumulate(C.byref(self.dev), 1 if keep_tables else 0, self.stream_handle()))
+        self._tables_held = bool(keep_tables)
 
     def vote_all(self):
         """Last streamed batch of unsorted input: k_consensus votes every tile from ``counts``
         (after ``accumulate(keep_tables=True)``)."""
         nt = int(self.db.info.n_tiles)
+        self._tables_held = False   # (k_consensus consumes and clears the insertion tables)
         if nt == 0:
             return
         self._all_tiles = torch.arange(nt, dtype=torch.int32, device=self.db.device)
@@ -474,7 +480,48 @@ class Workspace:
                                    cut, _ptr(text), total, st))
         return offs, text[:total], (stats.cpu().numpy().reshape(nt, 6) if stats is not None else None)
 
-    def run_with_tables(self, counts=True, sites=None, *, depth=None, lowcov=None):
+    def insertions_table(self, min_reads=1):
+        """The insertion events the batch keeps as the text of the insertion tables (table.py;
+        s2c_ins_len, the prefix sum, s2c_ins_write on the current stream): the return shape of
+        ``counts_table`` — tile k's lines at [offs[k], offs[k+1]).  Needs its preconditions and
+        the insertion tables still held: between ``accumulate(keep_tables=True)`` and
+        ``vote_all()``, which consumes them.  ``min_reads`` >= 1: the least reads of a listed
+        motif, applied after equal long motifs are counted together."""
+        if not self.keep_counts or self.tile_range is not None:
+            raise ValueError("insertions_table needs Workspace(keep_counts=True) over the whole batch")
+        if not self._counts_filled:
+            raise ValueError("insertions_table needs filled counts (accumulate; s2c_consensus zeroes them)")
+        if not self._tables_held:
+            raise ValueError("insertions_table needs the insertion tables: after accumulate(keep_tables=True), "
+                             "before vote_all()")
+        min_reads = int(min_reads)
+        if not 1 <= min_reads < 2 ** 32:
+            raise ValueError("insertions_table: 1 <= min_reads < 2^32")
+        i = self.db.info
+        dev = self.db.device
+        nt = int(i.n_tiles)
+        if nt == 0:
+            return np.zeros(1, dtype=np.int64), torch.empty(0, dtype=torch.uint8, device=dev)
+        st = self.stream_handle()
+        db = self.db
+        blocks = self._table_blocks()
+        n_bkt, n_lng = int(i.n_bkt), int(i.n_lng)
+        scratch = torch.empty(max(32 * (n_bkt + n_lng), 16), dtype=torch.uint8, device=dev)   # (s2c.h: the size rule)
+        offs_d = torch.zeros(nt + 1, dtype=torch.int64, device=dev)
+        lens = torch.empty(nt, dtype=torch.int64, device=dev)
+        L.check(lib.s2c_ins_len(_ptr(db.tiles), nt, _ptr(self.ibkt), n_bkt, _ptr(self.ilong), n_lng, _ptr(self.ilong_n),
+                                _ptr(db.bq), _ptr(db.bx), int(i.n_qwords), _ptr(self.counts), i.padded_len, _ptr(blocks),
+                                min_reads, _ptr(scratch), _ptr(lens), st))
+        torch.cumsum(lens, 0, out=offs_d[1:])
+        offs = offs_d.cpu().numpy()
+        total = int(offs[-1])
+        text = torch.empty(max(total, 16), dtype=torch.uint8, device=dev)
+        L.check(lib.s2c_ins_write(_ptr(db.tiles), nt, n_bkt, n_lng, _ptr(db.bq), _ptr(db.bx), int(i.n_qwords),
+                                  _ptr(self.counts), i.padded_len, _ptr(blocks), _ptr(scratch), _ptr(offs_d), _ptr(text),
+                                  total, st))
+        return offs, text[:total]
+
+    def run_with_tables(self, counts=True, sites=None, *, depth=None, lowcov=None, insertions=None):
         """``run()`` through the counts route, with any of the tables: every tile's counts
         stored (s2c_accumulate on zeroed counts, the insertion tables kept), formatted as text
         (before the vote, which leaves the counts zero), then every tile voted from them
@@ -483,7 +530,9 @@ class Workspace:
         Returns (counts_table() or None, sites_table(*sites) or None): a table not asked for
         is not formatted.  With ``depth`` = min_cov (the depth intervals, ``passed`` counted at
         min_cov) or ``lowcov`` = cut (the runs of coverage < cut), two more:
-        (..., depth_table(0, depth) or None, depth_table(lowcov) or None)."""
+        (..., depth_table(0, depth) or None, depth_table(lowcov) or None).  With ``insertions`` =
+        min_reads one more element, last: insertions_table(insertions) — formatted before the
+        vote consumes the insertion tables."""
         if not self.keep_counts:
             raise ValueError("run_with_tables needs Workspace(keep_counts=True)")
         if lowcov is not None and int(lowcov) < 1:
@@ -496,10 +545,10 @@ class Workspace:
         stable = self.sites_table(*sites) if sites is not None else None
         dtable = self.depth_table(0, depth) if depth is not None else None
         ltable = self.depth_table(lowcov) if lowcov is not None else None
+        itable = self.insertions_table(insertions) if insertions is not None else None
         self.vote_all()
-        if depth is None and lowcov is None:
-            return table, stable
-        return table, stable, dtable, ltable
+        res = (table, stable) if depth is None and lowcov is None else (table, stable, dtable, ltable)
+        return res if insertions is None else res + (itable,)
 
     def run_with_counts(self):
         """``run_with_tables`` with the count tables alone.  Returns counts_table()'s (offs,

@@ -28,6 +28,16 @@ maximal run of positions with coverage < max(-m, 1) — where the vote wrote the
 (sam2consensus.py:358).  The device finds and formats the runs (csrc/s2c_runs.hip,
 ``Workspace.depth_table``); ``depth_runs``, ``format_depth``, ``format_lowcov`` and
 ``depth_stats`` are the model.
+
+Insertion motif tables (``--insertions``): ``REF__PREFIX.insertions.tsv``, one line ``pos\tcov\t
+reads\tlen\tmotif`` per distinct (position, motif) among the insertion events the consensus is
+voted from (:73-75, :221, :262-271): ``pos`` the 1-based position whose consensus letter the
+inserted columns follow (:371-372), ``cov`` the coverage there (:294; it can be 0 or below
+``reads``: a read whose CIGAR ends in ``I`` does not cover its own key), ``reads`` the reads
+carrying exactly this motif, its length and its characters from ``-ACGNT``.  Lines are ordered
+by ``pos``, then ``reads`` falling, ``len`` rising, then the motif symbol by symbol in
+``-ACGNT`` order.  The device groups, orders and formats (csrc/s2c_ins.hip,
+``Workspace.insertions_table``); ``format_insertions`` is the model.
 """
 from __future__ import annotations
 
@@ -45,6 +55,8 @@ LOWCOV_SUFFIX = b".lowcov.tsv"
 SUMMARY_HEADER = b"ref\tlen\tcovered\tpassed\tsumcov\tmincov\tmaxcov\truns\n"
 SUMMARY_SUFFIX = b".depth_summary.tsv"
 EMPTY_STATS = (0, 0, 0, 0, 2 ** 63 - 1, -1)   # a block without a run start (s2c_runs_len)
+INS_HEADER = b"pos\tcov\treads\tlen\tmotif\n"
+INS_SUFFIX = b".insertions.tsv"
 
 
 def format_rows(counts_6xL, p0=1):
@@ -89,6 +101,24 @@ def format_sites(counts_6xL, p0=1, min_cov=1, min_alt=2, min_frac=0.05):
             int(p0) + j, cov, n[0], n[1], n[2], n[3], n[4], n[5], SYMBOLS[order[0]],
             "".join(SYMBOLS[s] for s in order[1:] if n[s]), alt * 10000 // cov))
     return "".join(out).encode("ascii")
+
+
+def format_insertions(entries, cov, p0=1, min_reads=1):
+    """The insertion lines (no header) of ``entries``: (pos, motif, reads) with ``pos`` the
+    0-based index into ``cov`` (the coverage per position), ``motif`` a non-empty string over
+    ``-ACGNT`` and ``reads`` >= 1, each (pos, motif) once; position ``p0`` is printed for index
+    0.  Entries with ``reads < min_reads`` are left out.  The order: ``pos`` rising, ``reads``
+    falling, ``len`` rising, the motif symbol by symbol in ``-ACGNT`` order."""
+    rows = []
+    for pos, motif, reads in entries:
+        motif = motif.decode("ascii") if isinstance(motif, (bytes, bytearray)) else str(motif)
+        if not motif or any(ch not in SYMBOLS for ch in motif):
+            raise ValueError("a motif is a non-empty string over -ACGNT")
+        if int(reads) >= int(min_reads):
+            rows.append((int(pos), -int(reads), len(motif), [SYMBOLS.index(ch) for ch in motif], motif))
+    rows.sort(key=lambda r: r[:4])
+    return "".join("%d\t%d\t%d\t%d\t%s\n" % (int(p0) + pos, int(cov[pos]), -nr, n, motif)
+                   for pos, nr, n, _, motif in rows).encode("ascii")
 
 
 def table_files(hb, prefix, offs, body, header=HEADER, suffix=SUFFIX):
