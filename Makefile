@@ -63,7 +63,7 @@ $(foreach s,$(sort prof poison $(V)),$(eval $(call DIAG_RULES,$(s))))
 ISA_DIR ?= /tmp/s2c_isa
 isa:
 	mkdir -p $(ISA_DIR)
-	for f in s2c_reads s2c_tile s2c_dense; do \
+	for f in $(KERNELS); do \
 	  $(HIPCC) $(HIPFLAGS) -c $(SRC)/$$f.hip -o $(ISA_DIR)/$$f.o -save-temps=obj \
 	    -Rpass-analysis=kernel-resource-usage 2> $(ISA_DIR)/$$f.resource_usage.txt; done
 

@@ -174,10 +174,10 @@ def consensus_batch(hb, thresholds, prefix, min_depth=1, fill=b"-", nchar=0, dev
         least = max(int(min_depth), 1)
         res = ws.run_with_tables(counts=bool(counts), sites=sites, depth=least if depth else None,
                                  lowcov=least if lowcov else None, insertions=insertions)
+        # (counts, sites[, depth, lowcov][, insertions]: run_with_tables' docstring)
         itab = res[-1] if insertions is not None else None
         ctab, stab = res[:2]
-        if runs:
-            dtab, ltab = res[2:4]
+        dtab, ltab = res[2:4] if runs else (None, None)
     else:
         ws.run()
     torch.cuda.synchronize(db.device)
@@ -192,20 +192,19 @@ def consensus_batch(hb, thresholds, prefix, min_depth=1, fill=b"-", nchar=0, dev
     for name, recs in fastas.items():
         files[name.encode("latin-1") + b"__" + pre + b".fasta"] = render(recs, nchar)
     if tables:   # (after build_records: a vote error raises and no file is returned)
-        from .table import (DEPTH_HEADER, DEPTH_SUFFIX, INS_HEADER, INS_SUFFIX, LOWCOV_HEADER, LOWCOV_SUFFIX, SITES_HEADER,
-                            SITES_SUFFIX, summary_file, table_files)
-        if counts:
-            files.update(table_files(hb, pre, ctab[0], to_host(ctab[1])))
-        if variants is not None:
-            files.update(table_files(hb, pre, stab[0], to_host(stab[1]), SITES_HEADER, SITES_SUFFIX))
-        if depth:
-            files.update(table_files(hb, pre, dtab[0], to_host(dtab[1]), DEPTH_HEADER, DEPTH_SUFFIX))
-        if lowcov:
-            files.update(table_files(hb, pre, ltab[0], to_host(ltab[1]), LOWCOV_HEADER, LOWCOV_SUFFIX))
-        if depth:   # (the host sums the tiles' statistics; it never reads the counts)
-            files.update(summary_file(hb, pre, dtab[2]))
-        if insertions is not None:
-            files.update(table_files(hb, pre, itab[0], to_host(itab[1]), INS_HEADER, INS_SUFFIX))
+        from . import table as tb
+
+        def text(tab, header, suffix):
+            return lambda: tb.table_files(hb, pre, tab[0], to_host(tab[1]), header, suffix)
+        # (the summary: the host sums the tiles' statistics; it never reads the counts)
+        for asked, make in ((counts, text(ctab, tb.HEADER, tb.SUFFIX)),
+                            (variants is not None, text(stab, tb.SITES_HEADER, tb.SITES_SUFFIX)),
+                            (depth, text(dtab, tb.DEPTH_HEADER, tb.DEPTH_SUFFIX)),
+                            (lowcov, text(ltab, tb.LOWCOV_HEADER, tb.LOWCOV_SUFFIX)),
+                            (depth, lambda: tb.summary_file(hb, pre, dtab[2])),
+                            (insertions is not None, text(itab, tb.INS_HEADER, tb.INS_SUFFIX))):
+            if asked:
+                files.update(make())
     t["format"] = time.perf_counter() - t0
     return files
 

@@ -153,13 +153,6 @@ __device__ __forceinline__ bool before(const InsArgs &d, const uint4 &J, uint32_
     return j < i;   // (equal lines: duplicate keys of a hand-built table)
 }
 
-__device__ __forceinline__ uint64_t cov_at(const InsArgs &d, uint64_t g) {
-    uint64_t cov = 0;
-#pragma unroll
-    for (uint32_t s = 0; s < NSYM; s++) cov += d.counts[s * (uint64_t)d.padded_len + g];
-    return cov;
-}
-
 // Workgroup barrier that also orders the workgroup's global (scratch) stores before its loads
 __device__ __forceinline__ void wg_sync() {
     __threadfence_block();
@@ -282,7 +275,7 @@ __global__ __launch_bounds__(TWG) void k_ins_len(const InsArgs d, int64_t *__res
             if (i != HOLE) {
                 const uint4 E = ent[i];
                 const uint32_t pos = e_pos(E);
-                len = ndig64((uint64_t)B.p0 + pos) + ndig64(cov_at(d, (uint64_t)B.a + pos)) + ndig32(E.z) +
+                len = ndig64((uint64_t)B.p0 + pos) + ndig64(cov_at(d.counts, (uint64_t)d.padded_len, (uint64_t)B.a + pos)) + ndig32(E.z) +
                       ndig32(e_len(E)) + e_len(E) + 5u;   // (< 2^24 + 64: a wave's sum fits 32 bits)
             }
             const uint32_t inc = wave_scan(len, lane);
@@ -306,33 +299,20 @@ __global__ __launch_bounds__(TWG) void k_ins_len(const InsArgs d, int64_t *__res
     }
 }
 
-// The tile's range of dst: no byte is stored outside [0, cap).  dec32 / dec64 write the decimal
-// digits of a value (dec64: < 2^41) backwards, ending before byte e; they return the first byte.
+// The tile's range of dst: no byte is stored outside [0, cap).  o[k] = ch is put(k, ch), so
+// put32 / put64 (s2c_text.h) write their digits through it.
 struct Out {
     uint8_t *d;
     uint64_t cap;
     __device__ __forceinline__ void put(uint64_t o, uint32_t ch) const {
         if (o < cap) d[o] = (uint8_t)ch;
     }
-    __device__ __forceinline__ uint64_t dec32(uint64_t e, uint32_t x) const {
-        do {
-            const uint32_t q = x / 10u;
-            put(--e, '0' + (x - q * 10u));
-            x = q;
-        } while (x);
-        return e;
-    }
-    __device__ __forceinline__ uint64_t dec64(uint64_t e, uint64_t v) const {
-        if (v < 1000000000ull) return dec32(e, (uint32_t)v);
-        uint32_t hi, lo;
-        split9(v, hi, lo);
-        for (int k = 0; k < 9; k++) {
-            const uint32_t q = lo / 10u;
-            put(--e, '0' + (lo - q * 10u));
-            lo = q;
-        }
-        return dec32(e, hi);
-    }
+    struct Byte {
+        const Out &out;
+        uint64_t o;
+        __device__ __forceinline__ void operator=(uint8_t ch) const { out.put(o, ch); }
+    };
+    __device__ __forceinline__ Byte operator[](uint64_t o) const { return Byte{*this, o}; }
 };
 
 // tile i's lines → dst[offs[i], offs[i+1]); never a byte outside that range
@@ -362,13 +342,13 @@ __global__ __launch_bounds__(TWG) void k_ins_write(const InsArgs d, const int64_
                 const uint64_t off = (uint64_t)O.y | ((uint64_t)O.z << 32);
                 uint64_t e = off + O.w - 1u - len;   // the byte after the tab before the motif
                 o.put(--e, '\t');
-                e = o.dec32(e, len);
+                e = put32(o, e, len);
                 o.put(--e, '\t');
-                e = o.dec32(e, E.z);
+                e = put32(o, e, E.z);
                 o.put(--e, '\t');
-                e = o.dec64(e, pos < (uint32_t)(B.b - B.a) ? cov_at(d, (uint64_t)B.a + pos) : 0ull);
+                e = put64(o, e, pos < (uint32_t)(B.b - B.a) ? cov_at(d.counts, (uint64_t)d.padded_len, (uint64_t)B.a + pos) : 0ull);
                 o.put(--e, '\t');
-                o.dec64(e, (uint64_t)B.p0 + pos);
+                put64(o, e, (uint64_t)B.p0 + pos);
                 if (e_long(E)) {
                     list[atomicAdd(&nlist, 1u)] = s;
                 } else {
@@ -393,8 +373,6 @@ __global__ __launch_bounds__(TWG) void k_ins_write(const InsArgs d, const int64_
         }
     }
 }
-
-unsigned ins_grid(int64_t n) { return (unsigned)std::min<int64_t>(n, 8 * 256 * 4); }
 
 int check_args(const uint32_t *tiles, int64_t n_tiles, int64_t n_bkt, int64_t n_lng, int64_t n_qwords, int64_t padded_len) {
     if (n_tiles < 0 || n_bkt < 0 || n_lng < 0 || n_qwords < 0 || padded_len < 0 || n_bkt >= (1ll << 32) || n_lng >= (1ll << 32))
@@ -426,9 +404,8 @@ extern "C" int s2c_ins_len(const uint32_t *tiles, int64_t n_tiles, const uint32_
     a.n_tiles = (uint64_t)n_tiles; a.n_bkt = (uint64_t)n_bkt; a.n_lng = (uint64_t)n_lng; a.n_qwords = (uint64_t)n_qwords;
     a.padded_len = padded_len;
     a.min_reads = (uint32_t)min_reads;
-    k_ins_len<<<ins_grid(n_tiles), TWG, 0, (hipStream_t)stream>>>(a, lens);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? S2C_OK : s2c_set_error(S2C_ERR_HIP, std::string("k_ins_len: ") + hipGetErrorString(e));
+    k_ins_len<<<text_grid(n_tiles), TWG, 0, (hipStream_t)stream>>>(a, lens);
+    return launched("k_ins_len");
 }
 
 extern "C" int s2c_ins_write(const uint32_t *tiles, int64_t n_tiles, int64_t n_bkt, int64_t n_lng, const uint32_t *bq,
@@ -451,7 +428,6 @@ extern "C" int s2c_ins_write(const uint32_t *tiles, int64_t n_tiles, int64_t n_b
     a.n_tiles = (uint64_t)n_tiles; a.n_bkt = (uint64_t)n_bkt; a.n_lng = (uint64_t)n_lng; a.n_qwords = (uint64_t)n_qwords;
     a.padded_len = padded_len;
     a.min_reads = 1u;
-    k_ins_write<<<ins_grid(n_tiles), TWG, 0, (hipStream_t)stream>>>(a, offs, dst, dst_len);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? S2C_OK : s2c_set_error(S2C_ERR_HIP, std::string("k_ins_write: ") + hipGetErrorString(e));
+    k_ins_write<<<text_grid(n_tiles), TWG, 0, (hipStream_t)stream>>>(a, offs, dst, dst_len);
+    return launched("k_ins_write");
 }

@@ -10,12 +10,10 @@
 // position) and leaves one bit per position, set where the class differs from the position
 // before: a wave covers 64 aligned positions, a lane's left neighbour comes from the lane
 // below (lane 0's from the word before, or from a load of position g − 1), the ballot is the
-// mask word.  k_runs_len and
-// k_runs_write walk a block's mask words and queue its set bits — the run starts — in LDS as
-// the sites walk does.  Two things a run needs that a site does not:
-//   - its end is the next start.  The queue's last entry is held back until the next one
-//     arrives: an emit fires when the queue holds more than TWG starts and takes TWG of them,
-//     lane k reading entries k and k + 1;
+// mask word.  k_runs_len and k_runs_write queue a block's set bits — the run starts — with
+// walk_mask (s2c_text.h) as the sites' kernels do.  Two things a run needs that a site does not:
+//   - its end is the next start.  The walk holds the queue's last entry back until the next one
+//     arrives (HOLD), and lane k of an emit reads entries k and k + 1;
 //   - the end of the block's last start lies past the block, possibly far (an uncovered
 //     stretch of 30 Mb is half a million mask words).  The whole workgroup looks it up: each
 //     lane reads RLOOK mask words per step, a ballot finds each wave's first non-zero word, the
@@ -30,19 +28,11 @@ namespace s2c {
 namespace {
 
 constexpr int RLINE = 34;                  // 10 + 10 digits of positions, 11 of coverage, 3 separators
-constexpr int RBUF = TWG * RLINE + 16;     // + the destination's misalignment (< 16)
-constexpr uint32_t RWORDS = TWG / 64;      // mask words per step of the walk
-constexpr uint32_t RQCAP = 2 * TWG;        // the queue: ≤ TWG starts left over + ≤ TWG new ones
+constexpr int RBUF = text_buf(RLINE);
 constexpr uint32_t MCHUNK = 8;             // consecutive mask words per wave of k_runs_mark
 constexpr uint32_t RLOOK = 2;              // mask words per lane and step of the end lookup
 constexpr int64_t NO_START = INT64_MAX;
 
-__device__ __forceinline__ uint64_t cov_at(const uint32_t *__restrict__ counts, uint64_t padded_len, uint64_t g) {
-    uint64_t cov = 0;
-#pragma unroll
-    for (uint32_t s = 0; s < NSYM; s++) cov += counts[s * padded_len + g];
-    return cov;
-}
 __device__ __forceinline__ uint64_t class_of(uint64_t cov, uint64_t cut) { return cut ? (uint64_t)(cov < cut) : cov; }
 
 // mask[w] bit l = class(64 w + l) != class(64 w + l − 1); bit 0 of word 0 set; bits at or past
@@ -52,7 +42,7 @@ __device__ __forceinline__ uint64_t class_of(uint64_t cov, uint64_t cut) { retur
 __global__ __launch_bounds__(TWG) void k_runs_mark(const uint32_t *__restrict__ counts, int64_t padded_len, uint64_t cut,
                                                     uint64_t *__restrict__ mask, uint64_t n_words) {
     const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t wave = (uint64_t)blockIdx.x * RWORDS + (threadIdx.x >> 6), n_waves = (uint64_t)gridDim.x * RWORDS;
+    const uint64_t wave = (uint64_t)blockIdx.x * MWORDS + (threadIdx.x >> 6), n_waves = (uint64_t)gridDim.x * MWORDS;
     for (uint64_t c = wave * MCHUNK; c < n_words; c += n_waves * MCHUNK) {
         uint64_t cls[MCHUNK];
 #pragma unroll
@@ -85,26 +75,16 @@ __device__ __forceinline__ RBlk load_rblk(const int64_t *__restrict__ blocks, co
     return RBlk{blocks[3 * i], blocks[3 * i + 1], blocks[3 * i + 2], refs[2 * i], refs[2 * i + 1]};
 }
 
-// the run starts of mask word w inside [a, b) (w one of the words [a, b) overlaps)
-__device__ __forceinline__ uint64_t start_word(const uint64_t *__restrict__ mask, int64_t w, const RBlk &B) {
-    uint64_t m = mask[w];
-    const int64_t lo = w << 6;
-    if (B.a == B.s && (B.s >> 6) == w) m |= 1ull << (B.s & 63);
-    if (B.a > lo) m &= ~0ull << (B.a - lo);
-    if (B.b < lo + 64) m &= ~0ull >> (lo + 64 - B.b);
-    return m;
-}
-
 // The first set bit of mask in [b, e), or e: the end of the run that holds position b − 1
 // (b < e).  The whole workgroup steps over the words, RLOOK per lane and step (their loads in
 // flight together): a ballot per word finds each wave's first non-zero one, the lowest
 // position of the waves wins; every lane returns the same.  One barrier per step: wfirst
-// [2][RWORDS] is used by the step's parity (a wave a step ahead writes the other half).
+// [2][MWORDS] is used by the step's parity (a wave a step ahead writes the other half).
 __device__ __forceinline__ int64_t next_start(const uint64_t *__restrict__ mask, int64_t b, int64_t e, int64_t *wfirst,
                                               uint32_t tid, uint32_t lane, uint32_t wv) {
     const int64_t w0 = b >> 6, wl = (e - 1) >> 6;
     uint32_t par = 0;
-    for (int64_t base = w0; base <= wl; base += RLOOK * TWG, par ^= RWORDS) {
+    for (int64_t base = w0; base <= wl; base += RLOOK * TWG, par ^= MWORDS) {
         uint64_t m[RLOOK];
 #pragma unroll
         for (uint32_t j = 0; j < RLOOK; j++) {
@@ -126,71 +106,48 @@ __device__ __forceinline__ int64_t next_start(const uint64_t *__restrict__ mask,
         lds_sync();
         int64_t best = NO_START;
 #pragma unroll
-        for (uint32_t k = 0; k < RWORDS; k++) best = wfirst[par + k] < best ? wfirst[par + k] : best;
+        for (uint32_t k = 0; k < MWORDS; k++) best = wfirst[par + k] < best ? wfirst[par + k] : best;
         if (best != NO_START) return best < e ? best : e;
     }
     return e;
 }
 
-// The walk both passes over a block share: its mask words RWORDS at a time (one per wave), the
-// run starts queued in LDS — a ring; each lane's slot its bit's rank — and emit(head, cnt,
-// tail) called on the queue's first cnt starts.  While the walk goes on an emit fires when the
-// queue holds more than TWG starts and takes TWG (tail < 0: the end of start k is entry k + 1,
-// which the queue holds); at the block's end it takes the rest, the last start's end = tail,
-// the next start past the block — not looked up when cut ≥ 1 and the last run's predicate is
-// false: it has no line, and its end is not used.  Every lane sees the same words, so the skips
-// and the calls of emit are the whole workgroup's.  emit starts with a barrier (the entries are in) and has
-// another between its reads of the queue and its end (the next entries land on slots it read).
+// walk_mask over block B's run starts: emit(head, cnt, tail) on the queue's first cnt starts.
+// While the walk goes on tail < 0: the end of start k is entry k + 1, which the queue holds.  At
+// the block's end the last start's end = tail, the next start past the block — not looked up
+// when cut ≥ 1 and the last run's predicate is false: it has no line, and its end is not used.
+// the run starts of mask word w inside [a, b) (w one of the words [a, b) overlaps)
+__device__ __forceinline__ uint64_t start_word(const uint64_t *__restrict__ mask, int64_t w, const RBlk &B) {
+    uint64_t m = mask[w];
+    const int64_t lo = w << 6;
+    if (B.a == B.s && (B.s >> 6) == w) m |= 1ull << (B.s & 63);   // (the bit at g == s forced on)
+    if (B.a > lo) m &= ~0ull << (B.a - lo);
+    if (B.b < lo + 64) m &= ~0ull >> (lo + 64 - B.b);
+    return m;
+}
+
 template <typename Emit>
-__device__ __forceinline__ void walk_runs(const uint32_t *__restrict__ counts, int64_t padded_len, uint64_t cut,
-                                          const uint64_t *__restrict__ mask, const RBlk &B, uint64_t *queue, int64_t *wfirst,
-                                          uint32_t tid, uint32_t lane, uint32_t wv, Emit emit) {
-    uint32_t qh = 0, qn = 0;   // the queue's head and fill
-    const int64_t wl = (B.b - 1) >> 6;   // the block's last mask word
-    for (int64_t wb = B.a >> 6; wb <= wl; wb += RWORDS) {
-        uint64_t m[RWORDS], any = 0;
-#pragma unroll
-        for (uint32_t w = 0; w < RWORDS; w++) {
-            m[w] = wb + w <= wl ? start_word(mask, wb + w, B) : 0ull;
-            any |= m[w];
-        }
-        if (!any) continue;
-        uint64_t mine = 0;
-        uint32_t pre = 0, tot = 0;
-#pragma unroll
-        for (uint32_t w = 0; w < RWORDS; w++) {
-            const uint32_t c = (uint32_t)__popcll(m[w]);
-            mine = w == wv ? m[w] : mine;
-            pre += w < wv ? c : 0u;
-            tot += c;
-        }
-        if ((mine >> lane) & 1u) {
-            const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(mine >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mine, 0u));
-            queue[(qh + qn + pre + rank) & (RQCAP - 1u)] = (uint64_t)(((wb + wv) << 6) + lane);
-        }
-        qn += tot;   // ≤ 2·TWG = RQCAP
-        if (qn > (uint32_t)TWG) {
-            emit(qh, (uint32_t)TWG, (int64_t)-1);
-            qh = (qh + TWG) & (RQCAP - 1u);
-            qn -= TWG;   // ≥ 1: the last start stays until its end is known
-        }
-    }
-    if (qn) {
+__device__ __forceinline__ void walk_block(const uint32_t *__restrict__ counts, int64_t padded_len, uint64_t cut,
+                                           const uint64_t *__restrict__ mask, const RBlk &B, uint64_t *queue, int64_t *wfirst,
+                                           uint32_t tid, uint32_t lane, uint32_t wv, Emit emit) {
+    const auto word = [](const uint64_t *__restrict__ mk, int64_t w, const RBlk &K) { return start_word(mk, w, K); };
+    const auto last = [&](uint32_t qh, uint32_t qn) {
         bool need = true;
         if (cut) {
             lds_sync();   // (the entries are in)
-            need = cov_at(counts, (uint64_t)padded_len, queue[(qh + qn - 1u) & (RQCAP - 1u)]) < cut;
+            need = cov_at(counts, (uint64_t)padded_len, queue[(qh + qn - 1u) & (QCAP - 1u)]) < cut;
         }
         const int64_t tail = need && B.b < B.e ? next_start(mask, B.b, B.e, wfirst, tid, lane, wv) : B.e;
         emit(qh, qn, tail);
-    }
+    };
+    walk_mask<true>(mask, B, word, queue, lane, wv, emit, last, (int64_t)-1);
 }
 
 // lane tid's run of an emit: its start g and end (exclusive)
 __device__ __forceinline__ void take_run(const uint64_t *queue, uint32_t qh, uint32_t cnt, int64_t tail, uint32_t tid,
                                          uint64_t &g, uint64_t &end) {
-    g = queue[(qh + tid) & (RQCAP - 1u)];
-    end = (tail < 0 || tid + 1u < cnt) ? queue[(qh + tid + 1u) & (RQCAP - 1u)] : (uint64_t)tail;
+    g = queue[(qh + tid) & (QCAP - 1u)];
+    end = (tail < 0 || tid + 1u < cnt) ? queue[(qh + tid + 1u) & (QCAP - 1u)] : (uint64_t)tail;
 }
 
 // bytes of the run's line: S and E the printed first and last position
@@ -223,9 +180,9 @@ __global__ __launch_bounds__(TWG) void k_runs_len(const uint32_t *__restrict__ c
                                                    const uint64_t *__restrict__ mask, const int64_t *__restrict__ blocks,
                                                    const int64_t *__restrict__ refs, uint64_t n, uint64_t cut, uint64_t min_cov,
                                                    int64_t *__restrict__ lens, int64_t *__restrict__ stats) {
-    __shared__ uint64_t queue[RQCAP];
-    __shared__ int64_t wfirst[2 * RWORDS];
-    __shared__ int64_t wacc[RWORDS][7];
+    __shared__ uint64_t queue[QCAP];
+    __shared__ int64_t wfirst[2 * MWORDS];
+    __shared__ int64_t wacc[MWORDS][7];
     S2C_POISON(queue, sizeof(queue));
     S2C_POISON(wfirst, sizeof(wfirst));
     S2C_POISON(wacc, sizeof(wacc));
@@ -236,7 +193,7 @@ __global__ __launch_bounds__(TWG) void k_runs_len(const uint32_t *__restrict__ c
         uint64_t sum = 0, runs = 0, covered = 0, passed = 0, sumcov = 0;
         int64_t mn = INT64_MAX, mx = -1;
         if (B.ok(padded_len) && B.a < B.b)
-            walk_runs(counts, padded_len, cut, mask, B, queue, wfirst, tid, lane, wv, [&](uint32_t qh, uint32_t cnt, int64_t tail) {
+            walk_block(counts, padded_len, cut, mask, B, queue, wfirst, tid, lane, wv, [&](uint32_t qh, uint32_t cnt, int64_t tail) {
                 lds_sync();
                 uint64_t g = 0, end = 0;
                 if (tid < cnt) take_run(queue, qh, cnt, tail, tid, g, end);
@@ -272,7 +229,7 @@ __global__ __launch_bounds__(TWG) void k_runs_len(const uint32_t *__restrict__ c
         lds_sync();
         if (tid == 0) {
             int64_t t[7] = {0, 0, 0, 0, 0, INT64_MAX, -1};
-            for (uint32_t w = 0; w < RWORDS; w++) {
+            for (uint32_t w = 0; w < MWORDS; w++) {
                 for (int k = 0; k < 5; k++) t[k] += wacc[w][k];
                 t[5] = wacc[w][5] < t[5] ? wacc[w][5] : t[5];
                 t[6] = wacc[w][6] > t[6] ? wacc[w][6] : t[6];
@@ -291,9 +248,9 @@ __global__ __launch_bounds__(TWG) void k_runs_write(const uint32_t *__restrict__
                                                      const int64_t *__restrict__ refs, const int64_t *__restrict__ offs,
                                                      uint64_t n, uint64_t cut, uint8_t *__restrict__ dst, int64_t dst_len) {
     __shared__ alignas(16) uint8_t buf[RBUF];
-    __shared__ uint64_t queue[RQCAP];
-    __shared__ int64_t wfirst[2 * RWORDS];
-    __shared__ uint32_t wtot[RWORDS];   // wave totals of the line lengths
+    __shared__ uint64_t queue[QCAP];
+    __shared__ int64_t wfirst[2 * MWORDS];
+    __shared__ uint32_t wtot[MWORDS];   // wave totals of the line lengths
     S2C_POISON(buf, RBUF);
     S2C_POISON(queue, sizeof(queue));
     S2C_POISON(wfirst, sizeof(wfirst));
@@ -306,8 +263,8 @@ __global__ __launch_bounds__(TWG) void k_runs_write(const uint32_t *__restrict__
         if (!B.ok(padded_len) || d0 < 0 || d1 < d0 || d1 > dst_len || B.a == B.b) continue;
         const uint64_t cap = (uint64_t)(d1 - d0);
         uint64_t done = 0;   // bytes of the block written so far
-        // cnt ≤ TWG queued starts, one line (or none) per lane, by k_table_write's scheme
-        walk_runs(counts, padded_len, cut, mask, B, queue, wfirst, tid, lane, wv, [&](uint32_t qh, uint32_t cnt, int64_t tail) {
+        // cnt ≤ TWG queued starts, one line (or none) per lane
+        walk_block(counts, padded_len, cut, mask, B, queue, wfirst, tid, lane, wv, [&](uint32_t qh, uint32_t cnt, int64_t tail) {
             lds_sync();   // (buf and wtot are no longer read either)
             const bool in = tid < cnt;
             uint64_t S = 0, E = 0, cov = 0;
@@ -320,31 +277,11 @@ __global__ __launch_bounds__(TWG) void k_runs_write(const uint32_t *__restrict__
                 E = S + (end - g) - 1u;
                 len = run_len(S, E, cov, cut);
             }
-            const uint32_t inc = wave_scan(len, lane);
-            if (lane == 63u) wtot[wv] = inc;
-            lds_sync();
-            uint32_t below = 0, tot = 0;
-#pragma unroll
-            for (uint32_t w = 0; w < RWORDS; w++) {
-                const uint32_t t = wtot[w];
-                below += w < wv ? t : 0u;
-                tot += t;
-            }
-            // the LDS image starts at the destination's offset inside its 16-byte word
-            uint8_t *d = dst + d0 + done;
-            const uint32_t sh = (uint32_t)((uintptr_t)d & 15u);
-            if (len) put_run(buf, sh + below + inc, S, E, cov, cut);   // the line's end ≤ 15 + TWG·RLINE < RBUF
-            lds_sync();
-            // (offs that do not match the lengths: the text is cut at the block's range)
-            const uint64_t left = cap - done;
-            if ((uint64_t)tot > left) tot = (uint32_t)left;
-            store_text(buf, d, sh, tot, tid);
-            done += tot;
+            done += emit_lines<RLINE>(buf, wtot, dst + d0, cap, done, len != 0u, len, tid, lane, wv,
+                                      [&](uint8_t *img, uint32_t e) { put_run(img, e, S, E, cov, cut); });
         });
     }
 }
-
-unsigned runs_grid(int64_t n) { return (unsigned)std::min<int64_t>(n, 8 * 256 * 4); }
 
 }  // namespace
 }  // namespace s2c
@@ -356,11 +293,10 @@ extern "C" int s2c_runs_mark(const uint32_t *counts, int64_t padded_len, int64_t
     if (padded_len == 0) return S2C_OK;
     if (!counts || !mask) return s2c_set_error(S2C_ERR_ARG, "NULL run table buffer");
     const int64_t n_words = (padded_len + 63) / 64;
-    const int64_t per_wg = RWORDS * MCHUNK;
+    const int64_t per_wg = MWORDS * MCHUNK;
     const unsigned grid = (unsigned)std::min<int64_t>((n_words + per_wg - 1) / per_wg, 8 * 256 * 8);
     k_runs_mark<<<grid, TWG, 0, (hipStream_t)stream>>>(counts, padded_len, (uint64_t)cut, mask, (uint64_t)n_words);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? S2C_OK : s2c_set_error(S2C_ERR_HIP, std::string("k_runs_mark: ") + hipGetErrorString(e));
+    return launched("k_runs_mark");
 }
 
 extern "C" int s2c_runs_len(const uint32_t *counts, int64_t padded_len, const uint64_t *mask, const int64_t *blocks,
@@ -372,10 +308,9 @@ extern "C" int s2c_runs_len(const uint32_t *counts, int64_t padded_len, const ui
     if (n == 0) return S2C_OK;
     if (!counts || !mask || !blocks || !refs || !lens || (cut == 0 && !stats))
         return s2c_set_error(S2C_ERR_ARG, "NULL run table buffer");
-    k_runs_len<<<runs_grid(n), TWG, 0, (hipStream_t)stream>>>(counts, padded_len, mask, blocks, refs, (uint64_t)n, (uint64_t)cut,
+    k_runs_len<<<text_grid(n), TWG, 0, (hipStream_t)stream>>>(counts, padded_len, mask, blocks, refs, (uint64_t)n, (uint64_t)cut,
                                                               (uint64_t)min_cov, lens, stats);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? S2C_OK : s2c_set_error(S2C_ERR_HIP, std::string("k_runs_len: ") + hipGetErrorString(e));
+    return launched("k_runs_len");
 }
 
 extern "C" int s2c_runs_write(const uint32_t *counts, int64_t padded_len, const uint64_t *mask, const int64_t *blocks,
@@ -386,8 +321,7 @@ extern "C" int s2c_runs_write(const uint32_t *counts, int64_t padded_len, const 
     if (cut < 0) return s2c_set_error(S2C_ERR_ARG, "run class: cut >= 0");
     if (n == 0) return S2C_OK;
     if (!counts || !mask || !blocks || !refs || !offs || !dst) return s2c_set_error(S2C_ERR_ARG, "NULL run table buffer");
-    k_runs_write<<<runs_grid(n), TWG, 0, (hipStream_t)stream>>>(counts, padded_len, mask, blocks, refs, offs, (uint64_t)n,
+    k_runs_write<<<text_grid(n), TWG, 0, (hipStream_t)stream>>>(counts, padded_len, mask, blocks, refs, offs, (uint64_t)n,
                                                                 (uint64_t)cut, dst, dst_len);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? S2C_OK : s2c_set_error(S2C_ERR_HIP, std::string("k_runs_write: ") + hipGetErrorString(e));
+    return launched("k_runs_write");
 }

@@ -12,22 +12,16 @@
 // per position: a wave covers 64 aligned positions and its ballot is the mask word.
 // k_sites_len and k_sites_write are k_table_len / k_table_write over that mask: one workgroup
 // per block {a, b, p0}, only the mask words over [a, b) read (1/8 B per position), the six
-// rows loaded for set bits alone.  Both walk the block four mask words (TWG positions) at a
-// time — a stretch without a set bit is skipped by the whole workgroup, no row load, no LDS,
-// no barrier — and queue the selected positions in LDS, each lane's slot its bit's rank (mbcnt
-// inside the word, popcounts of the words below); whenever the queue holds TWG positions, and
-// at the block's end, every lane takes one: dense row loads, and in k_sites_write one line per
-// lane with the count table's scheme (s2c_text.h): the scan of the line lengths, the LDS image
-// shifted by the destination's misalignment, 16-byte stores.
+// rows loaded for set bits alone: walk_mask (s2c_text.h) queues the selected positions, and
+// whenever the queue holds TWG of them, and at the block's end, every lane takes one: dense row
+// loads, and in k_sites_write one line per lane through emit_lines.
 #include "s2c_text.h"
 
 namespace s2c {
 namespace {
 
 constexpr int SLINE = TLINE + 15;          // + "\tM", "\tALT" (≤ 5 symbols), "\t0.dddd"
-constexpr int SBUF = TWG * SLINE + 16;     // + the destination's misalignment (< 16)
-constexpr uint32_t SWORDS = TWG / 64;      // mask words per step of the walk
-constexpr uint32_t SQCAP = 2 * TWG;        // the queue: < TWG positions left over + ≤ TWG new ones
+constexpr int SBUF = text_buf(SLINE);
 constexpr uint64_t SYMS = 0x544E4743412Dull;   // "-ACGNT", symbol s in byte s
 
 struct Rule {
@@ -86,7 +80,7 @@ __device__ __forceinline__ void put_site(uint8_t *buf, uint32_t e, const Row &r)
 __global__ __launch_bounds__(TWG) void k_sites_mark(const uint32_t *__restrict__ counts, int64_t padded_len, Rule R,
                                                      uint64_t *__restrict__ mask, uint64_t n_words) {
     const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t wave = (uint64_t)blockIdx.x * SWORDS + (threadIdx.x >> 6), n_waves = (uint64_t)gridDim.x * SWORDS;
+    const uint64_t wave = (uint64_t)blockIdx.x * MWORDS + (threadIdx.x >> 6), n_waves = (uint64_t)gridDim.x * MWORDS;
     for (uint64_t w = wave; w < n_words; w += n_waves) {
         const uint64_t g = w * 64u + lane;
         bool site = false;
@@ -105,54 +99,19 @@ __device__ __forceinline__ uint64_t blk_word(const uint64_t *__restrict__ mask, 
     return m;
 }
 
-// The walk both passes over a block share: its mask words SWORDS at a time (one per wave), the
-// selected positions queued in LDS — a ring; each lane's slot its bit's rank — and
-// emit(head, cnt) called on the queue's first cnt positions whenever it holds TWG of them, and
-// on the rest at the block's end.  Every lane of the workgroup sees the same words, so the
-// skip of a stretch without a set bit and the calls of emit are the whole workgroup's.  emit
-// starts with a barrier (the entries are in) and has another between its reads of the queue
-// and its end (the next entries land on the slots it read).
+// walk_mask over block B's sites: emit(head, cnt) on every TWG queued positions and on the rest
 template <typename Emit>
-__device__ __forceinline__ void walk_sites(const uint64_t *__restrict__ mask, const Blk &B, uint64_t *queue,
-                                           uint32_t lane, uint32_t wv, Emit emit) {
-    uint32_t qh = 0, qn = 0;   // the queue's head and fill
-    const int64_t wl = (B.b - 1) >> 6;   // the block's last mask word
-    for (int64_t wb = B.a >> 6; wb <= wl; wb += SWORDS) {
-        uint64_t m[SWORDS], any = 0;
-#pragma unroll
-        for (uint32_t w = 0; w < SWORDS; w++) {
-            m[w] = wb + w <= wl ? blk_word(mask, wb + w, B) : 0ull;
-            any |= m[w];
-        }
-        if (!any) continue;
-        uint64_t mine = 0;
-        uint32_t pre = 0, tot = 0;
-#pragma unroll
-        for (uint32_t w = 0; w < SWORDS; w++) {
-            const uint32_t c = (uint32_t)__popcll(m[w]);
-            mine = w == wv ? m[w] : mine;
-            pre += w < wv ? c : 0u;
-            tot += c;
-        }
-        if ((mine >> lane) & 1u) {
-            const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(mine >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mine, 0u));
-            queue[(qh + qn + pre + rank) & (SQCAP - 1u)] = (uint64_t)(((wb + wv) << 6) + lane);
-        }
-        qn += tot;   // < 2·TWG
-        if (qn >= (uint32_t)TWG) {
-            emit(qh, (uint32_t)TWG);
-            qh = (qh + TWG) & (SQCAP - 1u);
-            qn -= TWG;
-        }
-    }
-    if (qn) emit(qh, qn);
+__device__ __forceinline__ void walk_block(const uint64_t *__restrict__ mask, const Blk &B, uint64_t *queue, uint32_t lane,
+                                           uint32_t wv, Emit emit) {
+    const auto word = [](const uint64_t *__restrict__ mk, int64_t w, const Blk &K) { return blk_word(mk, w, K); };
+    walk_mask<false>(mask, B, word, queue, lane, wv, emit, emit);
 }
 
 // lens[i] = bytes of block i's site lines (0 for a block the guards refuse)
 __global__ __launch_bounds__(TWG) void k_sites_len(const uint32_t *__restrict__ counts, int64_t padded_len,
                                                     const uint64_t *__restrict__ mask, const int64_t *__restrict__ blocks,
                                                     uint64_t n, int64_t *__restrict__ lens) {
-    __shared__ uint64_t queue[SQCAP];
+    __shared__ uint64_t queue[QCAP];
     __shared__ uint64_t wsum[TWG / 64];
     S2C_POISON(queue, sizeof(queue));
     S2C_POISON(wsum, sizeof(wsum));
@@ -162,22 +121,14 @@ __global__ __launch_bounds__(TWG) void k_sites_len(const uint32_t *__restrict__ 
         const Blk B = load_blk(blocks, i);
         uint64_t sum = 0;
         if (B.ok(padded_len) && B.a < B.b)
-            walk_sites(mask, B, queue, lane, wv, [&](uint32_t qh, uint32_t cnt) {
+            walk_block(mask, B, queue, lane, wv, [&](uint32_t qh, uint32_t cnt) {
                 lds_sync();
-                const uint64_t g = tid < cnt ? queue[(qh + tid) & (SQCAP - 1u)] : 0;
+                const uint64_t g = tid < cnt ? queue[(qh + tid) & (QCAP - 1u)] : 0;
                 lds_sync();
                 if (tid < cnt)
                     sum += site_len(load_row(counts, (uint64_t)padded_len, g, (uint64_t)B.p0 + (g - (uint64_t)B.a)));
             });
-        sum = wave_sum(sum);
-        if (lane == 0) wsum[wv] = sum;
-        lds_sync();
-        if (tid == 0) {
-            uint64_t t = 0;
-            for (int w = 0; w < TWG / 64; w++) t += wsum[w];
-            lens[i] = (int64_t)t;
-        }
-        lds_sync();   // (wsum is written again for the next block)
+        block_total(sum, wsum, tid, &lens[i]);
     }
 }
 
@@ -187,7 +138,7 @@ __global__ __launch_bounds__(TWG) void k_sites_write(const uint32_t *__restrict_
                                                       const int64_t *__restrict__ offs, uint64_t n,
                                                       uint8_t *__restrict__ dst, int64_t dst_len) {
     __shared__ alignas(16) uint8_t buf[SBUF];
-    __shared__ uint64_t queue[SQCAP];
+    __shared__ uint64_t queue[QCAP];
     __shared__ uint32_t wtot[TWG / 64];   // wave totals of the line lengths
     S2C_POISON(buf, SBUF);
     S2C_POISON(queue, sizeof(queue));
@@ -200,43 +151,22 @@ __global__ __launch_bounds__(TWG) void k_sites_write(const uint32_t *__restrict_
         if (!B.ok(padded_len) || d0 < 0 || d1 < d0 || d1 > dst_len || B.a == B.b) continue;
         const uint64_t cap = (uint64_t)(d1 - d0);
         uint64_t run = 0;   // bytes of the block written so far
-        // cnt ≤ TWG queued positions, one line per lane, by k_table_write's scheme
-        walk_sites(mask, B, queue, lane, wv, [&](uint32_t qh, uint32_t cnt) {
+        // cnt ≤ TWG queued positions, one line per lane
+        walk_block(mask, B, queue, lane, wv, [&](uint32_t qh, uint32_t cnt) {
             lds_sync();   // (buf and wtot are no longer read either)
             const bool in = tid < cnt;
             Row r{};
             uint32_t len = 0;
             if (in) {
-                const uint64_t g = queue[(qh + tid) & (SQCAP - 1u)];
+                const uint64_t g = queue[(qh + tid) & (QCAP - 1u)];
                 r = load_row(counts, (uint64_t)padded_len, g, (uint64_t)B.p0 + (g - (uint64_t)B.a));
                 len = site_len(r);
             }
-            const uint32_t inc = wave_scan(len, lane);
-            if (lane == 63u) wtot[wv] = inc;
-            lds_sync();
-            uint32_t below = 0, tot = 0;
-#pragma unroll
-            for (uint32_t w = 0; w < TWG / 64; w++) {
-                const uint32_t t = wtot[w];
-                below += w < wv ? t : 0u;
-                tot += t;
-            }
-            // the LDS image starts at the destination's offset inside its 16-byte word
-            uint8_t *d = dst + d0 + run;
-            const uint32_t sh = (uint32_t)((uintptr_t)d & 15u);
-            if (in) put_site(buf, sh + below + inc, r);   // the line's end ≤ 15 + TWG·SLINE < SBUF
-            lds_sync();
-            // (offs that do not match the lengths: the text is cut at the block's range)
-            const uint64_t left = cap - run;
-            if ((uint64_t)tot > left) tot = (uint32_t)left;
-            store_text(buf, d, sh, tot, tid);
-            run += tot;
+            run += emit_lines<SLINE>(buf, wtot, dst + d0, cap, run, in, len, tid, lane, wv,
+                                     [&](uint8_t *img, uint32_t e) { put_site(img, e, r); });
         });
     }
 }
-
-// (5 workgroups of k_sites_write fit a CU's LDS)
-unsigned sites_grid(int64_t n) { return (unsigned)std::min<int64_t>(n, 8 * 256 * 4); }
 
 }  // namespace
 }  // namespace s2c
@@ -250,11 +180,10 @@ extern "C" int s2c_sites_mark(const uint32_t *counts, int64_t padded_len, int64_
     if (padded_len == 0) return S2C_OK;
     if (!counts || !mask) return s2c_set_error(S2C_ERR_ARG, "NULL site table buffer");
     const int64_t n_words = (padded_len + 63) / 64;
-    const unsigned grid = (unsigned)std::min<int64_t>((n_words + SWORDS - 1) / SWORDS, 8 * 256 * 8);
+    const unsigned grid = (unsigned)std::min<int64_t>((n_words + MWORDS - 1) / MWORDS, 8 * 256 * 8);
     k_sites_mark<<<grid, TWG, 0, (hipStream_t)stream>>>(counts, padded_len, Rule{(uint64_t)min_cov, (uint64_t)min_alt, min_frac},
                                                          mask, (uint64_t)n_words);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? S2C_OK : s2c_set_error(S2C_ERR_HIP, std::string("k_sites_mark: ") + hipGetErrorString(e));
+    return launched("k_sites_mark");
 }
 
 extern "C" int s2c_sites_len(const uint32_t *counts, int64_t padded_len, const uint64_t *mask, const int64_t *blocks,
@@ -263,9 +192,8 @@ extern "C" int s2c_sites_len(const uint32_t *counts, int64_t padded_len, const u
     if (n < 0 || padded_len < 0) return s2c_set_error(S2C_ERR_ARG, "bad site table sizes");
     if (n == 0) return S2C_OK;
     if (!counts || !mask || !blocks || !lens) return s2c_set_error(S2C_ERR_ARG, "NULL site table buffer");
-    k_sites_len<<<sites_grid(n), TWG, 0, (hipStream_t)stream>>>(counts, padded_len, mask, blocks, (uint64_t)n, lens);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? S2C_OK : s2c_set_error(S2C_ERR_HIP, std::string("k_sites_len: ") + hipGetErrorString(e));
+    k_sites_len<<<text_grid(n), TWG, 0, (hipStream_t)stream>>>(counts, padded_len, mask, blocks, (uint64_t)n, lens);
+    return launched("k_sites_len");
 }
 
 extern "C" int s2c_sites_write(const uint32_t *counts, int64_t padded_len, const uint64_t *mask, const int64_t *blocks,
@@ -274,8 +202,7 @@ extern "C" int s2c_sites_write(const uint32_t *counts, int64_t padded_len, const
     if (n < 0 || padded_len < 0 || dst_len < 0) return s2c_set_error(S2C_ERR_ARG, "bad site table sizes");
     if (n == 0) return S2C_OK;
     if (!counts || !mask || !blocks || !offs || !dst) return s2c_set_error(S2C_ERR_ARG, "NULL site table buffer");
-    k_sites_write<<<sites_grid(n), TWG, 0, (hipStream_t)stream>>>(counts, padded_len, mask, blocks, offs, (uint64_t)n, dst,
-                                                                  dst_len);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? S2C_OK : s2c_set_error(S2C_ERR_HIP, std::string("k_sites_write: ") + hipGetErrorString(e));
+    // (5 workgroups of k_sites_write fit a CU's LDS)
+    k_sites_write<<<text_grid(n), TWG, 0, (hipStream_t)stream>>>(counts, padded_len, mask, blocks, offs, (uint64_t)n, dst, dst_len);
+    return launched("k_sites_write");
 }

@@ -6,22 +6,18 @@
 // array (s2c_dev.counts after s2c_accumulate / s2c_pileup_counts, or a test's own) and know
 // nothing else of a batch: the caller cuts the positions into blocks {a, b, p0}.
 //
-// Lines have no fixed width, so the text takes two passes like the FASTA bodies' lengths and
-// gather: k_table_len sums each block's line lengths, the caller takes the exclusive prefix
-// sum, k_table_write formats block i into dst[offs[i], offs[i+1]).  Both are one workgroup per
-// block, grid-strided.  k_table_write walks its block in sub-blocks of TSUB positions, one per
-// lane: coalesced loads of the six rows, the line length per lane, a workgroup scan of the
-// lengths (DPP inside a row, the row and wave totals above it), every lane writes its line
-// into LDS at its scanned offset, and the sub-block's contiguous bytes leave with 16-byte
-// stores.  The LDS image is shifted by the destination's misalignment, so LDS reads and
-// global stores are both 16-byte aligned; head and tail bytes go out singly.
+// The dense table of the scheme in s2c_text.h: k_table_len sums each block's line lengths,
+// k_table_write walks its block in sub-blocks of TSUB positions, one per lane: coalesced loads
+// of the six rows, the line length per lane, and the write side of one line per lane, written
+// out here (emit_lines is the same lines for the walks' emits).
 #include "s2c_text.h"
 
 namespace s2c {
 namespace {
 
 constexpr int TSUB = TWG;            // positions per sub-block: one line per lane
-constexpr int TBUF = TSUB * TLINE + 16;   // + the destination's misalignment (< 16)
+constexpr int TBUF = text_buf(TLINE);
+static_assert(15 + TSUB * TLINE < TBUF, "the LDS image holds a sub-block's lines behind the destination's misalignment");
 
 // lens[i] = bytes of block i's text (0 for a block the guards refuse)
 __global__ __launch_bounds__(TWG) void k_table_len(const uint32_t *__restrict__ counts, int64_t padded_len,
@@ -36,15 +32,7 @@ __global__ __launch_bounds__(TWG) void k_table_len(const uint32_t *__restrict__ 
         if (B.ok(padded_len))
             for (int64_t g = B.a + threadIdx.x; g < B.b; g += TWG)
                 sum += line_len(load_row(counts, (uint64_t)padded_len, (uint64_t)g, (uint64_t)(B.p0 + (g - B.a))));
-        sum = wave_sum(sum);
-        if ((threadIdx.x & 63u) == 0) wsum[threadIdx.x >> 6] = sum;
-        lds_sync();
-        if (threadIdx.x == 0) {
-            uint64_t t = 0;
-            for (int w = 0; w < TWG / 64; w++) t += wsum[w];
-            lens[i] = (int64_t)t;
-        }
-        lds_sync();   // (wsum is written again for the next block)
+        block_total(sum, wsum, threadIdx.x, &lens[i]);
     }
 }
 
@@ -103,9 +91,6 @@ __global__ __launch_bounds__(TWG) void k_table_write(const uint32_t *__restrict_
     }
 }
 
-// (7 workgroups of k_table_write fit a CU's LDS: a grid of 8 per CU keeps them all busy)
-unsigned table_grid(int64_t n) { return (unsigned)std::min<int64_t>(n, 8 * 256 * 4); }
-
 }  // namespace
 }  // namespace s2c
 
@@ -115,9 +100,8 @@ extern "C" int s2c_table_len(const uint32_t *counts, int64_t padded_len, const i
     if (n < 0 || padded_len < 0) return s2c_set_error(S2C_ERR_ARG, "bad count table sizes");
     if (n == 0) return S2C_OK;
     if (!counts || !blocks || !lens) return s2c_set_error(S2C_ERR_ARG, "NULL count table buffer");
-    k_table_len<<<table_grid(n), TWG, 0, (hipStream_t)stream>>>(counts, padded_len, blocks, (uint64_t)n, lens);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? S2C_OK : s2c_set_error(S2C_ERR_HIP, std::string("k_table_len: ") + hipGetErrorString(e));
+    k_table_len<<<text_grid(n), TWG, 0, (hipStream_t)stream>>>(counts, padded_len, blocks, (uint64_t)n, lens);
+    return launched("k_table_len");
 }
 
 extern "C" int s2c_table_write(const uint32_t *counts, int64_t padded_len, const int64_t *blocks, const int64_t *offs,
@@ -126,8 +110,7 @@ extern "C" int s2c_table_write(const uint32_t *counts, int64_t padded_len, const
     if (n < 0 || padded_len < 0 || dst_len < 0) return s2c_set_error(S2C_ERR_ARG, "bad count table sizes");
     if (n == 0) return S2C_OK;
     if (!counts || !blocks || !offs || !dst) return s2c_set_error(S2C_ERR_ARG, "NULL count table buffer");
-    k_table_write<<<table_grid(n), TWG, 0, (hipStream_t)stream>>>(counts, padded_len, blocks, offs, (uint64_t)n, dst,
-                                                                  dst_len);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? S2C_OK : s2c_set_error(S2C_ERR_HIP, std::string("k_table_write: ") + hipGetErrorString(e));
+    // (7 workgroups of k_table_write fit a CU's LDS: a grid of 8 per CU keeps them all busy)
+    k_table_write<<<text_grid(n), TWG, 0, (hipStream_t)stream>>>(counts, padded_len, blocks, offs, (uint64_t)n, dst, dst_len);
+    return launched("k_table_write");
 }

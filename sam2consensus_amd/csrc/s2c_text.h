@@ -1,8 +1,18 @@
-// s2c_text.h — what the kernels that format counts as text share (s2c_table.hip, s2c_sites.hip,
-// s2c_runs.hip):
-// the decimal digit code, one position's row and its counts line, the workgroup's scan of line
-// lengths to offsets, the blocks {a, b, p0} with their guards, and the aligned store of a
-// sub-block's text out of its LDS image.
+// s2c_text.h — the scheme of the kernels that write tables as text (s2c_table.hip, s2c_sites.hip,
+// s2c_runs.hip, s2c_ins.hip); each of those files keeps its line's format and what it selects.
+//
+// Lines have no fixed width, so a table takes two launches over its blocks {a, b, p0}, one
+// workgroup per block, grid-strided: a length pass (block_total: lens[i] = bytes of block i's
+// lines), the caller's exclusive prefix sum, and a write pass of block i into
+// dst[offs[i], offs[i+1]).  The write pass goes TWG lines at a time, one per lane (emit_lines):
+// a workgroup scan of the line lengths (DPP inside a row, the row and wave totals above it),
+// every lane writes its line backwards into an LDS image at its scanned offset, and the image's
+// contiguous bytes leave with 16-byte stores (store_text).  The image is shifted by the
+// destination's misalignment, so LDS reads and global stores are both 16-byte aligned; head and
+// tail bytes go out singly.  A sparse table picks its lines by a mask of one bit per position
+// that a mark kernel left, and walk_mask queues a block's set bits for the two passes.
+// Also here: the decimal digit code, one position's row and its counts line, and the blocks
+// with their guards.
 #pragma once
 #include "s2c_common.h"
 
@@ -60,6 +70,13 @@ __device__ __forceinline__ Row load_row(const uint32_t *__restrict__ counts, uin
     r.pos = pos;
     return r;
 }
+// the coverage alone
+__device__ __forceinline__ uint64_t cov_at(const uint32_t *__restrict__ counts, uint64_t padded_len, uint64_t g) {
+    uint64_t cov = 0;
+#pragma unroll
+    for (uint32_t s = 0; s < NSYM; s++) cov += counts[s * padded_len + g];
+    return cov;
+}
 __device__ __forceinline__ uint32_t line_len(const Row &r) {
     uint32_t n = ndig64(r.pos) + ndig64(r.cov) + 8u;
 #pragma unroll
@@ -67,8 +84,11 @@ __device__ __forceinline__ uint32_t line_len(const Row &r) {
     return n;
 }
 
-// decimal digits of x written backwards, ending before byte `e` of buf; returns the first byte
-__device__ __forceinline__ uint32_t put32(uint8_t *buf, uint32_t e, uint32_t x) {
+// decimal digits of x written backwards, ending before byte `e` of buf; returns the first byte.
+// buf: anything that stores a byte by buf[o] = ch — an LDS image's pointer (emit_lines' bound
+// holds the lines inside it), or a guarded range of the destination (s2c_ins.hip's Out).
+template <typename Buf, typename I>
+__device__ __forceinline__ I put32(Buf buf, I e, uint32_t x) {
     do {
         const uint32_t q = x / 10u;
         buf[--e] = (uint8_t)('0' + (x - q * 10u));
@@ -76,7 +96,9 @@ __device__ __forceinline__ uint32_t put32(uint8_t *buf, uint32_t e, uint32_t x) 
     } while (x);
     return e;
 }
-__device__ __forceinline__ uint32_t put64(uint8_t *buf, uint32_t e, uint64_t v) {
+// (v < 2^41)
+template <typename Buf, typename I>
+__device__ __forceinline__ I put64(Buf buf, I e, uint64_t v) {
     if (v < 1000000000ull) return put32(buf, e, (uint32_t)v);
     uint32_t hi, lo;
     split9(v, hi, lo);
@@ -118,6 +140,116 @@ __device__ __forceinline__ void store_text(const uint8_t *buf, uint8_t *d, uint3
     for (uint32_t k = lo + tid; k < min(vlo, hi); k += TWG) d16[k] = buf[k];
     for (uint32_t k = vlo + 16u * tid; k < vhi; k += 16u * TWG) *(uint4 *)(d16 + k) = *(const uint4 *)(buf + k);
     for (uint32_t k = max(vhi, vlo) + tid; k < hi; k += TWG) d16[k] = buf[k];
+}
+
+// The write side of one line per lane (k_sites_write, k_runs_write; k_table_write keeps its own
+// copy of these lines: through this function its sub-block loop compiled to other instructions).
+// Lane tid (lane of wave wv) has a line iff `has`, of len bytes (0 without one); put(buf, end)
+// writes it backwards, ending before byte `end` of the LDS image buf.  The lines go, in lane
+// order, to d0[run, ...), cut at d0[cap); returns the bytes stored (the same in every lane).
+// wtot: TWG / 64 words of LDS for the waves' totals, which no lane still reads when the call
+// starts (the walks' emits start with a barrier).  buf is written only past the first barrier
+// inside, which every lane's reads of the call before (store_text) precede.
+template <int LINE, int BUF, typename Put>
+__device__ __forceinline__ uint32_t emit_lines(uint8_t (&buf)[BUF], uint32_t *wtot, uint8_t *d0, uint64_t cap, uint64_t run,
+                                               bool has, uint32_t len, uint32_t tid, uint32_t lane, uint32_t wv, Put put) {
+    static_assert(15 + TWG * LINE < BUF, "the LDS image holds TWG lines behind the destination's misalignment");
+    // inclusive scan of the lengths: the wave's, then the waves below
+    const uint32_t inc = wave_scan(len, lane);
+    if (lane == 63u) wtot[wv] = inc;
+    lds_sync();
+    uint32_t below = 0, tot = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < TWG / 64; w++) {
+        const uint32_t t = wtot[w];
+        below += w < wv ? t : 0u;
+        tot += t;
+    }
+    // the LDS image starts at the destination's offset inside its 16-byte word
+    uint8_t *d = d0 + run;
+    const uint32_t sh = (uint32_t)((uintptr_t)d & 15u);
+    if (has) put(buf, sh + below + inc);   // the line's end ≤ 15 + TWG·LINE
+    lds_sync();
+    // (offs that do not match the lengths: the text is cut at the block's range)
+    const uint64_t left = cap - run;
+    if ((uint64_t)tot > left) tot = (uint32_t)left;
+    store_text(buf, d, sh, tot, tid);
+    return tot;
+}
+constexpr int text_buf(int line) { return TWG * line + 16; }   // + the destination's misalignment (< 16)
+
+// The length side: out[0] = Σ of sum over the workgroup (wsum: a word of LDS per wave).
+__device__ __forceinline__ void block_total(uint64_t sum, uint64_t *wsum, uint32_t tid, int64_t *out) {
+    sum = wave_sum(sum);
+    if ((tid & 63u) == 0) wsum[tid >> 6] = sum;
+    lds_sync();
+    if (tid == 0) {
+        uint64_t t = 0;
+        for (int w = 0; w < TWG / 64; w++) t += wsum[w];
+        *out = (int64_t)t;
+    }
+    lds_sync();   // (wsum is written again for the next block)
+}
+
+constexpr uint32_t MWORDS = TWG / 64;      // mask words per step of the walk: one per wave
+constexpr uint32_t QCAP = 2 * TWG;         // the queue: ≤ TWG positions left over + ≤ TWG new ones
+
+// The walk both passes of a sparse table make over a block B = [a, b), a < b: its mask words,
+// word(mask, w, B) each one's bits inside the block, MWORDS at a time (one per wave); the set
+// bits' positions queued in LDS — a ring of QCAP; each lane's slot its bit's rank (mbcnt inside
+// the word, popcounts of the words below) — and emit(head, TWG, mid...) called on the queue's
+// first TWG positions whenever it holds TWG of them (HOLD: more than TWG, so the last one stays
+// queued until its successor is — a line that needs the next position finds it at the next
+// slot), and finish(head, cnt) on the rest, 1 ≤ cnt ≤ TWG, at the block's end.  A stretch
+// without a set bit is skipped: no LDS, no barrier.  Every lane of the workgroup sees the same
+// words, so the skips and the calls of emit and finish are the whole workgroup's.  Both start
+// with a barrier (the entries are in, and what the call before read is no longer read) and have
+// another between their reads of the queue and their end (the next entries land on the slots
+// they read).  (word is the file's own function, and emit is called with the caller's own
+// arguments, not through a wrapper: either changed the order of the step's instructions.)
+template <bool HOLD, typename Blk, typename Word, typename Emit, typename Finish, typename... Mid>
+__device__ __forceinline__ void walk_mask(const uint64_t *__restrict__ mask, const Blk &B, Word word, uint64_t *queue,
+                                          uint32_t lane, uint32_t wv, Emit emit, Finish finish, Mid... mid) {
+    uint32_t qh = 0, qn = 0;   // the queue's head and fill
+    const int64_t wl = (B.b - 1) >> 6;   // the block's last mask word
+    for (int64_t wb = B.a >> 6; wb <= wl; wb += MWORDS) {
+        uint64_t m[MWORDS], any = 0;
+#pragma unroll
+        for (uint32_t w = 0; w < MWORDS; w++) {
+            m[w] = wb + w <= wl ? word(mask, wb + w, B) : 0ull;
+            any |= m[w];
+        }
+        if (!any) continue;
+        uint64_t mine = 0;
+        uint32_t pre = 0, tot = 0;
+#pragma unroll
+        for (uint32_t w = 0; w < MWORDS; w++) {
+            const uint32_t c = (uint32_t)__popcll(m[w]);
+            mine = w == wv ? m[w] : mine;
+            pre += w < wv ? c : 0u;
+            tot += c;
+        }
+        if ((mine >> lane) & 1u) {
+            const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(mine >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mine, 0u));
+            queue[(qh + qn + pre + rank) & (QCAP - 1u)] = (uint64_t)(((wb + wv) << 6) + lane);
+        }
+        qn += tot;   // ≤ 2·TWG = QCAP (< without HOLD)
+        if (HOLD ? qn > (uint32_t)TWG : qn >= (uint32_t)TWG) {
+            emit(qh, (uint32_t)TWG, mid...);
+            qh = (qh + TWG) & (QCAP - 1u);
+            qn -= TWG;
+        }
+    }
+    if (qn) finish(qh, qn);
+}
+
+// the grid of a table's len and write kernels over n blocks: 8 workgroups per CU
+inline unsigned text_grid(int64_t n) { return (unsigned)std::min<int64_t>(n, 8 * 256 * 4); }
+
+// a launcher's last line: S2C_OK, or the launch's error as "<kernel>: <what HIP says>"
+inline int launched(const char *kernel) {
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? S2C_OK : s2c_set_error(S2C_ERR_HIP, std::string(kernel) + ": " + hipGetErrorString(e));
 }
 
 }  // namespace s2c

@@ -371,63 +371,73 @@ class Workspace:
             self._tblocks = _up(blocks.reshape(-1), self.db.device)
         return self._tblocks
 
+    def _two_pass(self, name, len_call, write_call, own_checks=None, filled_by="accumulate / pileup_counts"):
+        """What the text tables share, for the method ``name``: its preconditions —
+        keep_counts=True over the whole batch (every tile's counts in HBM) and counts a
+        counts-only stage has filled —, then the method's ``own_checks()``, then on the current
+        stream ``len_call(nt, blocks, lens, st)``, the launches that leave tile k's bytes in
+        ``lens[k]`` (it allocates what the method needs besides), the prefix sum, the one host
+        read of the offsets, and ``write_call(nt, blocks, offs, text, total, st)``, the launch
+        that formats tile k into text[offs[k], offs[k+1]) (``blocks``: ``_table_blocks``; all
+        buffers as pointers).  Returns (offs[n_tiles + 1] int64 numpy, device uint8 tensor of
+        exactly offs[-1] bytes); a batch without tiles gives the empty pair: no allocation, no
+        launch."""
+        if not self.keep_counts or self.tile_range is not None:
+            raise ValueError(name + " needs Workspace(keep_counts=True) over the whole batch")
+        if not self._counts_filled:
+            raise ValueError(name + " needs filled counts (" + filled_by + "; s2c_consensus zeroes them)")
+        if own_checks is not None:
+            own_checks()
+        dev = self.db.device
+        nt = int(self.db.info.n_tiles)
+        if nt == 0:
+            return np.zeros(1, dtype=np.int64), torch.empty(0, dtype=torch.uint8, device=dev)
+        st = self.stream_handle()
+        blocks = _ptr(self._table_blocks())
+        offs_d = torch.zeros(nt + 1, dtype=torch.int64, device=dev)
+        lens = torch.empty(nt, dtype=torch.int64, device=dev)
+        len_call(nt, blocks, _ptr(lens), st)
+        torch.cumsum(lens, 0, out=offs_d[1:])
+        offs = offs_d.cpu().numpy()
+        total = int(offs[-1])
+        text = torch.empty(max(total, 16), dtype=torch.uint8, device=dev)
+        write_call(nt, blocks, _ptr(offs_d), _ptr(text), total, st)
+        return offs, text[:total]
+
+    def _mask_words(self):
+        """A bit per position of ``counts`` for a mark kernel (device int64, ≥ 1 word)."""
+        return torch.empty(max((int(self.db.info.padded_len) + 63) // 64, 1), dtype=torch.int64, device=self.db.device)
+
     def counts_table(self):
         """The filled ``counts`` as the text of the count tables (table.py; s2c_table_len, the
         prefix sum, s2c_table_write on the current stream): (offs[n_tiles + 1] int64 numpy,
         device uint8 tensor of exactly offs[-1] bytes) — tile k's rows at [offs[k], offs[k+1]),
         a reference's table its tiles' rows in order.  Needs keep_counts=True (every tile's
         counts in HBM) and counts a counts-only stage has filled."""
-        if not self.keep_counts or self.tile_range is not None:
-            raise ValueError("counts_table needs Workspace(keep_counts=True) over the whole batch")
-        if not self._counts_filled:
-            raise ValueError("counts_table needs filled counts (accumulate / pileup_counts; s2c_consensus zeroes them)")
-        i = self.db.info
-        dev = self.db.device
-        nt = int(i.n_tiles)
-        if nt == 0:
-            return np.zeros(1, dtype=np.int64), torch.empty(0, dtype=torch.uint8, device=dev)
-        st = self.stream_handle()
-        blocks = self._table_blocks()
-        offs_d = torch.zeros(nt + 1, dtype=torch.int64, device=dev)
-        lens = torch.empty(nt, dtype=torch.int64, device=dev)
-        L.check(lib.s2c_table_len(_ptr(self.counts), i.padded_len, _ptr(blocks), nt, _ptr(lens), st))
-        torch.cumsum(lens, 0, out=offs_d[1:])
-        offs = offs_d.cpu().numpy()
-        total = int(offs[-1])
-        text = torch.empty(max(total, 16), dtype=torch.uint8, device=dev)
-        L.check(lib.s2c_table_write(_ptr(self.counts), i.padded_len, _ptr(blocks), _ptr(offs_d), nt, _ptr(text),
-                                    total, st))
-        return offs, text[:total]
+        Lp = self.db.info.padded_len
+
+        def len_call(nt, blocks, lens, st):
+            L.check(lib.s2c_table_len(_ptr(self.counts), Lp, blocks, nt, lens, st))
+
+        def write_call(nt, blocks, offs, text, total, st):
+            L.check(lib.s2c_table_write(_ptr(self.counts), Lp, blocks, offs, nt, text, total, st))
+        return self._two_pass("counts_table", len_call, write_call)
 
     def sites_table(self, min_cov=1, min_alt=2, min_frac=0.05):
         """The filled ``counts`` as the text of the tables of mixed sites (table.py;
         s2c_sites_mark into a bit per position, then s2c_sites_len, the prefix sum and
         s2c_sites_write over the set bits, on the current stream): the return shape and the
         preconditions of ``counts_table`` — tile k's site lines at [offs[k], offs[k+1])."""
-        if not self.keep_counts or self.tile_range is not None:
-            raise ValueError("sites_table needs Workspace(keep_counts=True) over the whole batch")
-        if not self._counts_filled:
-            raise ValueError("sites_table needs filled counts (accumulate / pileup_counts; s2c_consensus zeroes them)")
-        i = self.db.info
-        dev = self.db.device
-        nt = int(i.n_tiles)
-        if nt == 0:
-            return np.zeros(1, dtype=np.int64), torch.empty(0, dtype=torch.uint8, device=dev)
-        st = self.stream_handle()
-        blocks = self._table_blocks()
-        mask = torch.empty(max((int(i.padded_len) + 63) // 64, 1), dtype=torch.int64, device=dev)
-        offs_d = torch.zeros(nt + 1, dtype=torch.int64, device=dev)
-        lens = torch.empty(nt, dtype=torch.int64, device=dev)
-        L.check(lib.s2c_sites_mark(_ptr(self.counts), i.padded_len, int(min_cov), int(min_alt), float(min_frac),
-                                   _ptr(mask), st))
-        L.check(lib.s2c_sites_len(_ptr(self.counts), i.padded_len, _ptr(mask), _ptr(blocks), nt, _ptr(lens), st))
-        torch.cumsum(lens, 0, out=offs_d[1:])
-        offs = offs_d.cpu().numpy()
-        total = int(offs[-1])
-        text = torch.empty(max(total, 16), dtype=torch.uint8, device=dev)
-        L.check(lib.s2c_sites_write(_ptr(self.counts), i.padded_len, _ptr(mask), _ptr(blocks), _ptr(offs_d), nt,
-                                    _ptr(text), total, st))
-        return offs, text[:total]
+        Lp, buf = self.db.info.padded_len, {}
+
+        def len_call(nt, blocks, lens, st):
+            c, mask = _ptr(self.counts), _ptr(buf.setdefault("mask", self._mask_words()))
+            L.check(lib.s2c_sites_mark(c, Lp, int(min_cov), int(min_alt), float(min_frac), mask, st))
+            L.check(lib.s2c_sites_len(c, Lp, mask, blocks, nt, lens, st))
+
+        def write_call(nt, blocks, offs, text, total, st):
+            L.check(lib.s2c_sites_write(_ptr(self.counts), Lp, _ptr(buf["mask"]), blocks, offs, nt, text, total, st))
+        return self._two_pass("sites_table", len_call, write_call)
 
     def _table_refs(self):
         """Device int64 [n_tiles][2] {s, e}: the global range of the reference each tile lies in
@@ -450,35 +460,27 @@ class Workspace:
         — the lines of the runs that start in tile k at [offs[k], offs[k+1]); ``stats`` int64
         numpy [n_tiles][6] {runs, covered, passed, sumcov, mincov, maxcov} of those runs
         (``passed``: coverage >= min_cov), or None when cut >= 1."""
-        if not self.keep_counts or self.tile_range is not None:
-            raise ValueError("depth_table needs Workspace(keep_counts=True) over the whole batch")
-        if not self._counts_filled:
-            raise ValueError("depth_table needs filled counts (accumulate / pileup_counts; s2c_consensus zeroes them)")
-        cut, min_cov = int(cut), int(min_cov)
-        if cut < 0 or min_cov < 0:
-            raise ValueError("depth_table: cut >= 0 and min_cov >= 0")
-        i = self.db.info
-        dev = self.db.device
-        nt = int(i.n_tiles)
-        if nt == 0:
-            return (np.zeros(1, dtype=np.int64), torch.empty(0, dtype=torch.uint8, device=dev),
-                    None if cut else np.zeros((0, 6), dtype=np.int64))
-        st = self.stream_handle()
-        blocks, refs = self._table_blocks(), self._table_refs()
-        mask = torch.empty(max((int(i.padded_len) + 63) // 64, 1), dtype=torch.int64, device=dev)
-        offs_d = torch.zeros(nt + 1, dtype=torch.int64, device=dev)
-        lens = torch.empty(nt, dtype=torch.int64, device=dev)
-        stats = None if cut else torch.empty(nt * 6, dtype=torch.int64, device=dev)
-        L.check(lib.s2c_runs_mark(_ptr(self.counts), i.padded_len, cut, _ptr(mask), st))
-        L.check(lib.s2c_runs_len(_ptr(self.counts), i.padded_len, _ptr(mask), _ptr(blocks), _ptr(refs), nt, cut, min_cov,
-                                 _ptr(lens), _ptr(stats) if stats is not None else None, st))
-        torch.cumsum(lens, 0, out=offs_d[1:])
-        offs = offs_d.cpu().numpy()
-        total = int(offs[-1])
-        text = torch.empty(max(total, 16), dtype=torch.uint8, device=dev)
-        L.check(lib.s2c_runs_write(_ptr(self.counts), i.padded_len, _ptr(mask), _ptr(blocks), _ptr(refs), _ptr(offs_d), nt,
-                                   cut, _ptr(text), total, st))
-        return offs, text[:total], (stats.cpu().numpy().reshape(nt, 6) if stats is not None else None)
+        Lp, buf = self.db.info.padded_len, {}
+
+        def own_checks():
+            if int(cut) < 0 or int(min_cov) < 0:
+                raise ValueError("depth_table: cut >= 0 and min_cov >= 0")
+
+        def len_call(nt, blocks, lens, st):
+            c, refs, mask = _ptr(self.counts), _ptr(self._table_refs()), _ptr(buf.setdefault("mask", self._mask_words()))
+            if not int(cut):
+                buf["stats"] = torch.empty(nt * 6, dtype=torch.int64, device=self.db.device)
+            L.check(lib.s2c_runs_mark(c, Lp, int(cut), mask, st))
+            L.check(lib.s2c_runs_len(c, Lp, mask, blocks, refs, nt, int(cut), int(min_cov), lens, _ptr(buf.get("stats")), st))
+
+        def write_call(nt, blocks, offs, text, total, st):
+            L.check(lib.s2c_runs_write(_ptr(self.counts), Lp, _ptr(buf["mask"]), blocks, _ptr(self._table_refs()), offs, nt,
+                                       int(cut), text, total, st))
+        offs, text = self._two_pass("depth_table", len_call, write_call, own_checks)
+        if int(cut):
+            return offs, text, None
+        stats = buf["stats"].cpu().numpy() if "stats" in buf else np.zeros(0, dtype=np.int64)
+        return offs, text, stats.reshape(-1, 6)
 
     def insertions_table(self, min_reads=1):
         """The insertion events the batch keeps as the text of the insertion tables (table.py;
@@ -487,39 +489,26 @@ class Workspace:
         the insertion tables still held: between ``accumulate(keep_tables=True)`` and
         ``vote_all()``, which consumes them.  ``min_reads`` >= 1: the least reads of a listed
         motif, applied after equal long motifs are counted together."""
-        if not self.keep_counts or self.tile_range is not None:
-            raise ValueError("insertions_table needs Workspace(keep_counts=True) over the whole batch")
-        if not self._counts_filled:
-            raise ValueError("insertions_table needs filled counts (accumulate; s2c_consensus zeroes them)")
-        if not self._tables_held:
-            raise ValueError("insertions_table needs the insertion tables: after accumulate(keep_tables=True), "
-                             "before vote_all()")
-        min_reads = int(min_reads)
-        if not 1 <= min_reads < 2 ** 32:
-            raise ValueError("insertions_table: 1 <= min_reads < 2^32")
-        i = self.db.info
-        dev = self.db.device
-        nt = int(i.n_tiles)
-        if nt == 0:
-            return np.zeros(1, dtype=np.int64), torch.empty(0, dtype=torch.uint8, device=dev)
-        st = self.stream_handle()
-        db = self.db
-        blocks = self._table_blocks()
-        n_bkt, n_lng = int(i.n_bkt), int(i.n_lng)
-        scratch = torch.empty(max(32 * (n_bkt + n_lng), 16), dtype=torch.uint8, device=dev)   # (s2c.h: the size rule)
-        offs_d = torch.zeros(nt + 1, dtype=torch.int64, device=dev)
-        lens = torch.empty(nt, dtype=torch.int64, device=dev)
-        L.check(lib.s2c_ins_len(_ptr(db.tiles), nt, _ptr(self.ibkt), n_bkt, _ptr(self.ilong), n_lng, _ptr(self.ilong_n),
-                                _ptr(db.bq), _ptr(db.bx), int(i.n_qwords), _ptr(self.counts), i.padded_len, _ptr(blocks),
-                                min_reads, _ptr(scratch), _ptr(lens), st))
-        torch.cumsum(lens, 0, out=offs_d[1:])
-        offs = offs_d.cpu().numpy()
-        total = int(offs[-1])
-        text = torch.empty(max(total, 16), dtype=torch.uint8, device=dev)
-        L.check(lib.s2c_ins_write(_ptr(db.tiles), nt, n_bkt, n_lng, _ptr(db.bq), _ptr(db.bx), int(i.n_qwords),
-                                  _ptr(self.counts), i.padded_len, _ptr(blocks), _ptr(scratch), _ptr(offs_d), _ptr(text),
-                                  total, st))
-        return offs, text[:total]
+        db, i, buf = self.db, self.db.info, {}
+        Lp, nq, n_bkt, n_lng = i.padded_len, int(i.n_qwords), int(i.n_bkt), int(i.n_lng)
+
+        def own_checks():
+            if not self._tables_held:
+                raise ValueError("insertions_table needs the insertion tables: after accumulate(keep_tables=True), "
+                                 "before vote_all()")
+            if not 1 <= int(min_reads) < 2 ** 32:
+                raise ValueError("insertions_table: 1 <= min_reads < 2^32")
+
+        def len_call(nt, blocks, lens, st):
+            buf["scratch"] = torch.empty(max(32 * (n_bkt + n_lng), 16), dtype=torch.uint8, device=db.device)   # (s2c.h: the size rule)
+            L.check(lib.s2c_ins_len(_ptr(db.tiles), nt, _ptr(self.ibkt), n_bkt, _ptr(self.ilong), n_lng, _ptr(self.ilong_n),
+                                    _ptr(db.bq), _ptr(db.bx), nq, _ptr(self.counts), Lp, blocks, int(min_reads),
+                                    _ptr(buf["scratch"]), lens, st))
+
+        def write_call(nt, blocks, offs, text, total, st):
+            L.check(lib.s2c_ins_write(_ptr(db.tiles), nt, n_bkt, n_lng, _ptr(db.bq), _ptr(db.bx), nq, _ptr(self.counts), Lp,
+                                      blocks, _ptr(buf["scratch"]), offs, text, total, st))
+        return self._two_pass("insertions_table", len_call, write_call, own_checks, filled_by="accumulate")
 
     def run_with_tables(self, counts=True, sites=None, *, depth=None, lowcov=None, insertions=None):
         """``run()`` through the counts route, with any of the tables: every tile's counts

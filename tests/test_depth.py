@@ -19,6 +19,7 @@ import pytest
 import golden_io
 import s2c_oracle as o
 import test_table as tt
+from devmem import _ptr, _stream
 
 from sam2consensus_amd import table
 
@@ -274,17 +275,6 @@ def _model_blocks(c, rows, cut, min_cov):
                   min(st[4], v), max(st[5], v)]
         out.append(("".join(lines).encode(), tuple(st)))
     return out
-
-
-def _ptr(t):
-    import ctypes as C
-    return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _stream():
-    import ctypes as C
-    import torch
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def _dev_counts(c):

@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 import batch_model as bm
+from devmem import _ptr
 import golden_io
 import s2c_oracle as o
 import test_table as tt
@@ -307,11 +308,6 @@ class Scene:
             e = [(pos, m, n) for (pos, m), n in d.items() if pos < b - a] if ok else []
             out.append(table.format_insertions(e, [int(v) for v in cov[a:b]] if ok else [], p0, min_reads))
         return out
-
-
-def _ptr(t):
-    import ctypes as C
-    return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
 def _u32(a):

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import batch_model as bm
+from devmem import _dev_i64
 import golden_io
 import s2c_oracle as o
 
@@ -147,11 +148,6 @@ def _synthetic_counts():
                   for s, st in enumerate((1, 3, 7, 9, 11, 13))]).astype(np.uint32)
     c[:, STRETCH[0]:STRETCH[1]] = 4294967295
     return c
-
-
-def _dev_i64(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64).reshape(-1)).cuda()
 
 
 def _table_len(counts_d, blocks):

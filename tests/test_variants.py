@@ -16,6 +16,7 @@ import pytest
 import golden_io
 import s2c_oracle as o
 import test_table as tt
+from devmem import _ptr, _stream
 
 from sam2consensus_amd import table
 
@@ -234,10 +235,11 @@ TIE_ROWS = [(0, 5, 5, 0, 0, 2), (3, 3, 3, 3, 3, 3), (0, 0, 0, 2, 0, 2), (7, 0, 0
             (2, 2, 9, 0, 0, 0), (0, 0, 6, 6, 1, 1), (1, 1, 1, 1, 1, 8), (0, 12, 0, 12, 0, 12), (5, 0, 5, 0, 4, 4)]
 # test_table.py's blocks (lengths 0, 1, 63, 64, 65, 255, 256, 257 and 2048, odd starts, the 9→10
 # and 9999→10000 steps, 10-digit positions) and blocks over the stretches above: odd starts that
-# share mask words with their neighbours, and blocks that overlap
-BLOCKS = tt.BLOCKS + [(1100, 2100, 1), (2100, 2305, 9), (2305, 2561, 1), (2561, 2817, 9998), (2623, 2624, 5),
-                      (2624, 2816, 1), (2500, 3500, 999999000), (3399, 3465, 1), (3465, 3830, 97), (3700, 3830, 1),
-                      (1050, 1051, 9999999999), (1281, 1791, 1), (1216, 1920, 1)]
+# share mask words with their neighbours, blocks that overlap, and two inside SOLID with exactly
+# 256 and 257 sites (the queue emits at 256: none left over, and one)
+BLOCKS = tt.BLOCKS + [(1100, 2100, 1), (1900, 2156, 1), (1901, 2158, 77), (2100, 2305, 9), (2305, 2561, 1),
+                      (2561, 2817, 9998), (2623, 2624, 5), (2624, 2816, 1), (2500, 3500, 999999000), (3399, 3465, 1),
+                      (3465, 3830, 97), (3700, 3830, 1), (1050, 1051, 9999999999), (1281, 1791, 1), (1216, 1920, 1)]
 PARAMS = [(1, 1, 0.0), (3, 2, 0.1)]
 
 
@@ -275,6 +277,8 @@ def test_synthetic_counts_hold_what_the_kernel_test_needs():
         assert e.any() and not e.all()
         assert m[tt.STRETCH[0]:tt.STRETCH[1]].all()
         assert m[:1000].any()
+        assert (1900, 2156, 1) in BLOCKS and (1901, 2158, 77) in BLOCKS
+        assert int(m[1900:2156].sum()) == 256 and int(m[1901:2158].sum()) == 257   # the queue emits at 256: none left, one left
     assert not table.site_mask(c, *PARAMS[1])[:1000].all()      # (the digit ladder: sites and others mixed)
     assert {g % 256 for g in SINGLES} >= {0, 63, 64, 255}
     a, b = (table.site_mask(c, *prm)[EDGES[0]:EDGES[1]] for prm in PARAMS)
@@ -284,17 +288,6 @@ def test_synthetic_counts_hold_what_the_kernel_test_needs():
 def _dev_u8(a):
     import torch
     return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1)).cuda()
-
-
-def _ptr(t):
-    import ctypes as C
-    return C.c_void_p(t.data_ptr())
-
-
-def _stream():
-    import ctypes as C
-    import torch
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def _sites_mark(counts_d, prm, padded=PADDED):
