@@ -395,6 +395,34 @@ int  s2c_batch_layers(s2c_batch *b);
 int  s2c_batch_layers_mode(s2c_batch *b, int with_dense);
 int  s2c_batch_info_get(const s2c_batch *b, s2c_batch_info *out);
 int  s2c_batch_arrays_get(const s2c_batch *b, s2c_batch_arrays *out);
+
+/* The dense windows' extension: what k_tile_dense's walk would derive from each window's compact
+ * piece records (dpc), written once by the host where it writes dpc.  Five arrays of u32 words,
+ * a row of dext per dense item (in dwin's order: filter dext's rows as dwin's):
+ *   drun   [n_drun][2]  run records.  Window i's block is records [dext[i][0], + nslot) — one per
+ *          op slot of the window (nslot = o1 − o0), in slot order, the block's first record at an
+ *          even index (16-byte aligned; an odd block is followed by one zero record).  The slot of
+ *          a S2C_PF_SIMPLE piece holds its run {rs | (rs + take) << 16, 16·qh' − rs} (rs, qh' and
+ *          take = the length field as in the piece's dpc record); every other slot is zero.
+ *   dnev   [n_dnev]     'N' events of the S2C_PF_SIMPLE | S2C_PF_XFEW pieces: the tile-relative
+ *          position rs + off − 2048 of every listed offset off < take that lies inside the tile's
+ *          words, [0, 32·⌈(b − a) / 32⌉).  Window i's are [dext[i][2], + dext[i][3]).
+ *   dxs    [n_dxs]      op slots (window-relative) of the S2C_PF_SIMPLE pieces with S2C_PF_X and
+ *          without S2C_PF_XFEW: runs whose non-ACGT chars are read from the planes.  Window i's
+ *          are [dext[i][4], + dext[i][5]).
+ *   drare  [n_drare][S2C_DPC_WORDS]  the dpc records of the pieces that are neither
+ *          S2C_PF_SIMPLE nor S2C_PF_LONG (a long piece starting in the window adds nothing to its
+ *          tile: its slots stay zero), in window order.  Window i's are [dext[i][6], + dext[i][7]).
+ *   dext   [n_dext][S2C_DEXT_WORDS]  {drun0, nslot, dnev0, n, dxs0, n, drare0, n} per dense item.
+ * s2c_batch_dense_ext_get fills the struct with host pointers into the batch (valid until
+ * s2c_batch_free; an empty array has a valid pointer and count 0); the same struct with device
+ * pointers is the argument of s2c_run_ext / s2c_pileup_ext. */
+#define S2C_DEXT_WORDS 8
+typedef struct {
+    const uint32_t *drun, *dnev, *dxs, *drare, *dext;
+    int64_t n_drun, n_dnev, n_dxs, n_drare, n_dext;   /* records / entries / rows (not words) */
+} s2c_dense_ext;
+int  s2c_batch_dense_ext_get(const s2c_batch *b, s2c_dense_ext *out);
 /* The sub-batch of tiles [t0, t1) for one GPU of a multi-GPU run (positions keep their
  * global coordinates; free it with s2c_batch_free). */
 int  s2c_batch_shard(const s2c_batch *b, int64_t t0, int64_t t1, s2c_batch **out);
@@ -518,6 +546,14 @@ int s2c_pileup(const s2c_dev *d, void *stream);
 int s2c_consensus(const s2c_dev *d, void *stream);
 /* all three, in order, on one stream (graph-capturable: no allocation, no sync) */
 int s2c_run(const s2c_dev *d, void *stream);
+/* s2c_pileup / s2c_run with the dense windows' extension (s2c_dense_ext, device pointers; dext
+ * filtered like dwin): k_tile_dense takes each window's run records by LDS-DMA from drun and
+ * walks only the pieces of drare, instead of deriving both from dpc — the same results.  ext =
+ * NULL is s2c_pileup / s2c_run; with an extension s2c_dev.dpc is not read and may be NULL.
+ * S2C_ERR_ARG before any launch (after s2c_dev's own checks): a NULL array with a non-zero count,
+ * a negative count, drun not 16-byte aligned, or n_dext != s2c_dev.n_dense. */
+int s2c_pileup_ext(const s2c_dev *d, const s2c_dense_ext *ext, void *stream);
+int s2c_run_ext(const s2c_dev *d, const s2c_dense_ext *ext, void *stream);
 
 /* (ABI 14) FASTA body assembly on the device (:394-418; replaces the host gather of the
  * output's body slots, s2c_gather_bodies): dst[offs[i], offs[i+1]) = out[starts[i], +len)

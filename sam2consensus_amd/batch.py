@@ -107,6 +107,15 @@ class HostBatch:
         self.px = _view(a.px, i.n_pieces, np.uint32)   # non-ACGT SEQ offsets of S2C_PF_XFEW pieces
         self.dwin = _view(a.dwin, i.n_dense * L.S2C_DWIN_WORDS, np.uint32).reshape(-1, L.S2C_DWIN_WORDS)
         self.dpc = _view(a.dpc, i.n_dpc * L.S2C_DPC_WORDS, np.uint32).reshape(-1, L.S2C_DPC_WORDS)
+        # the dense windows' extension (s2c_dense_ext): run records, 'N' events, X-run slots, the
+        # rare pieces' records, and each window's {first, count} in the four
+        x = L.DenseExt()
+        L.check(lib.s2c_batch_dense_ext_get(self._b, C.byref(x)))
+        self.drun = _view(x.drun, 2 * x.n_drun, np.uint32).reshape(-1, 2)
+        self.dnev = _view(x.dnev, x.n_dnev, np.uint32)
+        self.dxs = _view(x.dxs, x.n_dxs, np.uint32)
+        self.drare = _view(x.drare, x.n_drare * L.S2C_DPC_WORDS, np.uint32).reshape(-1, L.S2C_DPC_WORDS)
+        self.dext = _view(x.dext, x.n_dext * L.S2C_DEXT_WORDS, np.uint32).reshape(-1, L.S2C_DEXT_WORDS)
         self.lp = _view(a.lp, i.n_long, np.uint32)
         self.wtile = _view(a.wtile, i.n_words, np.uint32)
         self.names = [lib.s2c_batch_ref_name(self._b, k).decode("latin-1") for k in range(i.n_refs)]

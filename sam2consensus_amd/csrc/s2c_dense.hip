@@ -16,7 +16,11 @@
 //              in SEQ) by the general parsecigar + maxdel walk (:46-82, :210).  Runs of reads
 //              holding other N / '-' chars are queued too: their SEQ chars go into the
 //              per-position byte counters in one dense pass.
-//   3. count   the G = 64 / (tile words) lanes of a word count the runs covering it — A C G T
+//              With the windows' extension (s2c.h s2c_dense_ext, k_tile_dense<·, true>) the
+//              host has done the common piece's part: the window's run records arrive by a
+//              third DMA, the 'N' events and X-run slots as lists, and thread i takes rare
+//              piece i from the window's own list — no lean walk, no compaction.
+//   3. count  the G = 64 / (tile words) lanes of a word count the runs covering it — A C G T
 //              into bit-sliced Harley–Seal counters, 8 records at a time.
 //   4. vote    each lane holds 8 / G counter rows (a row = positions 8j + r, j = 0..3, one
 //              byte each — the transposed counters' own layout, and the byte counters' layout
@@ -79,6 +83,10 @@ struct DenseArgs {
     uint32_t buf_bytes;                                        // the window's LDS (16-byte multiple)
     int32_t n_thr, min_depth;
     const uint8_t *fill;   // the one -f char
+    // the windows' extension (s2c.h s2c_dense_ext; k_tile_dense<·, true>): run records, 'N'
+    // events, X-run slots, rare pieces' records, the windows' rows; the end of the DMA source
+    const uint32_t *drun, *dnev, *dxs, *drare, *dext;
+    const void *drun_end;
 };
 
 // The token walk of walk_piece (s2c_common.h: parsecigar :64-81 + maxdel :210) in 32-bit
@@ -205,6 +213,7 @@ __device__ __forceinline__ uint32_t lds_addr(const void *p) {
     return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void *)p;
 }
 typedef int v4i __attribute__((ext_vector_type(4)));
+typedef int v8i __attribute__((ext_vector_type(8)));
 typedef int v16i __attribute__((ext_vector_type(16)));
 // Scalar loads of uniform read-only words (tile records, items): s_load through the scalar
 // cache, waited here — the compiler would otherwise emit vector loads (the kernel stores to
@@ -439,13 +448,28 @@ __device__ __forceinline__ uint32_t byte_bits(uint32_t m) { return ((m & 0x80808
 struct Win {
     uint32_t tile, a, n, cb0, pf0, npc, o0, nslot, qw0, nqw, W0, nwords, lp0, nlong, dpc0;
 };
-__device__ __forceinline__ Win win_of(const DenseArgs &d, uint32_t item) {
+// ... and its row of the extension (S2C_DEXT_WORDS; nslot is the window's own)
+struct XWin {
+    uint32_t run0, nev0, nnev, xs0, nxs, rare0, nrare;
+};
+template <bool EXT>
+__device__ __forceinline__ Win win_of(const DenseArgs &d, uint32_t item, XWin &xw) {
     Win v;
     // the item's window (S2C_DWIN_WORDS, built by the host from the tile record) in one
-    // scalar round trip
+    // scalar round trip, the extension's row beside it
     v16i r;
-    asm volatile("s_load_dwordx16 %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)"
-                 : "=s"(r) : "s"(uni_ptr(d.dwin + (size_t)item * S2C_DWIN_WORDS)) : "memory");
+    if constexpr (EXT) {
+        v8i x;
+        asm volatile("s_load_dwordx16 %0, %2, 0x0\n\ts_load_dwordx8 %1, %3, 0x0\n\ts_waitcnt lgkmcnt(0)"
+                     : "=&s"(r), "=&s"(x)
+                     : "s"(uni_ptr(d.dwin + (size_t)item * S2C_DWIN_WORDS)), "s"(uni_ptr(d.dext + (size_t)item * S2C_DEXT_WORDS))
+                     : "memory");
+        xw = XWin{(uint32_t)x[0], (uint32_t)x[2], (uint32_t)x[3], (uint32_t)x[4], (uint32_t)x[5], (uint32_t)x[6], (uint32_t)x[7]};
+    } else {
+        xw = XWin{};
+        asm volatile("s_load_dwordx16 %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)"
+                     : "=s"(r) : "s"(uni_ptr(d.dwin + (size_t)item * S2C_DWIN_WORDS)) : "memory");
+    }
     v.tile = (uint32_t)r[0];
     v.a = (uint32_t)r[1];
     v.n = (uint32_t)r[2] - v.a;
@@ -470,7 +494,8 @@ struct WinLds {
     const uint32_t *opl;
     const uint2 *bql;
     uint2 *runl;
-    uint32_t *q;   // [nslot]: queued pieces (window index) from the front, X-run slots from the back
+    uint32_t *q;   // [nslot + 128]: queued pieces (window index) from the front, X-run slots from the back
+                   // (with the extension: the X-run slots of the rare pass alone, a wave from either end)
 };
 __device__ __forceinline__ const uint32_t *phase16(const uint8_t *region, const void *src) {
     return (const uint32_t *)(region + ((uintptr_t)src & 15));
@@ -488,11 +513,17 @@ __device__ __forceinline__ WinLds win_lds(const DenseArgs &d, const Win &v, uint
 }
 // issue the LDS-DMA of window v into buf, shared by the tile's waves (completion: every wave's
 // s_waitcnt vmcnt(0), then a barrier)
-template <int WPT>
-__device__ __forceinline__ void win_issue(const DenseArgs &d, const Win &v, uint8_t *buf) {
+template <int WPT, bool EXT>
+__device__ __forceinline__ void win_issue(const DenseArgs &d, const Win &v, const XWin &xw, uint8_t *buf) {
     dma16<WPT>(buf, d.ops + v.o0, v.nslot, d.ops_end);
     buf += dma16_bytes(v.nslot);
     dma16<WPT>(buf, d.bq + 2 * (size_t)v.qw0, 2 * v.nqw, d.bq_end);
+    if constexpr (EXT) {
+        // the window's run records onto runl (its block starts 16-byte aligned: phase 0; the
+        // last 16 bytes of an odd block carry the host's zero pad record onto a RUN_PAD record)
+        buf += dma16_bytes(2 * v.nqw);
+        dma16<WPT>(buf, d.drun + 2 * (size_t)xw.run0, 2 * v.nslot, d.drun_end);
+    }
 }
 
 // One tile of NWP words from its window in LDS, WPT waves (WT threads): a wave holds NWP / WPT
@@ -501,8 +532,10 @@ __device__ __forceinline__ void win_issue(const DenseArgs &d, const Win &v, uint
 constexpr int WPT = 2;   // waves per tile (they share the window)
 constexpr int WT = WGD * WPT;     // threads per tile
 constexpr int PFN = 2;   // piece records per thread loaded with the DMA (windows of ≤ PFN·WT pieces)
-template <int NWP>
-__device__ __forceinline__ void dense_tile(const DenseArgs &d, const Win &v, const WinLds &L, uint32_t *dcnt,
+// EXT: the walk from the windows' extension (xw; Pc[0] = this thread's rare record, Pc[1].x its
+// 'N' event), the run records already in runl.
+template <int NWP, bool EXT>
+__device__ __forceinline__ void dense_tile(const DenseArgs &d, const Win &v, const XWin &xw, const WinLds &L, uint32_t *dcnt,
                                            uint32_t *ncnt, uint32_t *ccnt, const uint8_t *amb, uint32_t fill0,
                                            const uint3 (&Pc)[PFN],
                                            uint32_t cw0, uint32_t cw1, unsigned long long t_entry,
@@ -526,9 +559,17 @@ __device__ __forceinline__ void dense_tile(const DenseArgs &d, const Win &v, con
     const uint32_t *opl = L.opl, *bxl = d.bx + qw0;
     const uint2 *bql = L.bql;
     uint2 *runl = L.runl;
-    // this wave's queue: 64 entries per walk iteration (its pieces' share of the window)
-    const uint32_t nitw = (npc + WT - 1) / WT, qcap = WGD * nitw;
-    uint32_t *queue = L.q + wv * qcap;
+    // this wave's queue: 64 entries per walk iteration (its pieces' share of the window).
+    // With the extension, the one queue of the tile holds the X runs of the rare pass's
+    // deletion reads alone, wave 0's from the front and wave 1's from the back.  Capacity rule:
+    // a deletion read adds at most 2 entries and owns 3 op slots, so the entries written are
+    // ≤ min(2·nrare, ⅔·nslot) ≤ qcap = min(2·nrare, nslot + 128), the queue's share of the
+    // window's LDS (S2C_DENSE_BYTES): the two ends never meet.
+    static_assert(!EXT || WPT == 2, "the X-run queue has two ends");
+    const uint32_t nitw = (npc + WT - 1) / WT, qcap = EXT ? min(2u * xw.nrare, v.nslot + 128u) : WGD * nitw;
+    uint32_t *queue = EXT ? L.q : L.q + wv * qcap;
+    const bool qback = !EXT || uni(wv) != 0u;   // this wave's X runs go in from the back
+    auto xslot = [&](uint32_t i) { return qback ? qcap - 1u - i : i; };
 
     // ---- walk: one lane per piece → run records (rec_enc) of the bases.  The one-token read
     //      (S2C_PF_SIMPLE, 99 % of C5's pieces) takes the lean path below; every other piece
@@ -544,7 +585,7 @@ __device__ __forceinline__ void dense_tile(const DenseArgs &d, const Win &v, con
     // nx); a round whose deletion reads' X runs (≤ 2 entries each) might not fit there sends
     // those reads through the general walk, which scans their planes itself and queues nothing.
     uint32_t nslow = 0, nx = 0;   // queue lengths (uniform)
-    const uint32_t nit = ABL(4) ? 0u : nitw;
+    const uint32_t nit = (EXT || ABL(4)) ? 0u : nitw;
     // one M / = / X token and nothing else: seqout = SEQ[0 : take] (:64-69), take in the
     // record's length field (s2c.h S2C_PF_SIMPLE): no op word read, no min
     auto lean = [&](uint32_t k, const uint3 P) {
@@ -572,46 +613,14 @@ __device__ __forceinline__ void dense_tile(const DenseArgs &d, const Win &v, con
             nslow += (uint32_t)__popcll(bs);
         }
         if (bxm) {
-            if (x1) queue[qcap - 1u - nx - mbcnt(bxm)] = D.j;
+            if (x1) queue[xslot(nx + mbcnt(bxm))] = D.j;
             nx += (uint32_t)__popcll(bxm);
         }
     };
-#pragma unroll
-    for (int u = 0; u < PFN; u++)
-        if ((uint32_t)u < nit) lean(tid + WT * u, Pc[u]);
-    for (uint32_t it = PFN; it < nit; it++) {   // (windows of more than WT·PFN pieces)
-        const uint32_t k = tid + WT * it;
-        lean(k, k < npc ? dpc_load(d, v.dpc0 + k) : make_uint3(0u, 0u, 0u));
-    }
-    // (the queued work below is this wave's own — its queue, its pieces' run records, atomic
-    // byte-counter adds — so its LDS writes completing is enough: the other wave's records are
-    // needed only by the count, after the barrier that ends the queued walks)
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    PROF_MARK(2);
-    // queued pieces, one per lane and round.  A piece's record comes from the lane that loaded
-    // it (ds_bpermute, all lanes on).
-    for (uint32_t base = 0; base < (ABL(16) ? 0u : nslow); base += WGD) {
-        const uint32_t i = base + lane;
-        const bool on = i < nslow;
-        const uint32_t k = on ? queue[i] : 0u, it = k / WT;
-        const int src = (int)(4 * (k % WGD));   // (k ≡ this wave's lane mod 64: WT is a multiple of 64)
-        uint32_t c0 = 0, c1 = 0, pxv = 0;
-#pragma unroll
-        for (int u = 0; u < PFN; u++) {
-            const uint32_t px = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)Pc[u].x);
-            const uint32_t py = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)Pc[u].y);
-            const uint32_t pz = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)Pc[u].z);
-            const bool me = it == (uint32_t)u;
-            c0 = me ? px : c0;
-            c1 = me ? py : c1;
-            pxv = me ? pz : pxv;
-        }
-        if (on && it >= (uint32_t)PFN) {   // (windows of more than WT·PFN pieces)
-            const uint3 R = dpc_load(d, v.dpc0 + k);
-            c0 = R.x;
-            c1 = R.y;
-            pxv = R.z;
-        }
+    // One piece that is not SIMPLE, from its compact record {c0, c1, pxv} (on: the lane holds
+    // one), shared by both paths; room: the X-run entries this round may add (the old path's
+    // capacity rule; the extension's queue always has room)
+    auto rare_piece = [&](bool on, uint32_t c0, uint32_t c1, uint32_t pxv, uint32_t room) {
         const DPiece D = dpc_dec(c0, c1);
         const uint32_t fl = D.fl, slen = D.slen, j = D.j, q = D.q;
         // bases, D / N / P, bases (the deletion reads) with no maxdel count to take (the rule is
@@ -634,10 +643,7 @@ __device__ __forceinline__ void dense_tile(const DenseArgs &d, const Win &v, con
         const bool xq = fdel && (fl & S2C_PF_X) != 0u && !xfew;
         bool x2 = xq && t2 > 0u;
         uint64_t bx1 = __ballot(xq), bx2 = __ballot(x2);
-        // (front entries [base + 64, nslow) are still to be read: the back stays above nslow
-        // until the last round, which has read every front entry)
-        const uint32_t room = qcap - (base + WGD < nslow ? nslow : 0u);
-        if (bx1 && nx + (uint32_t)(__popcll(bx1) + __popcll(bx2)) > room) {
+        if (!EXT && bx1 && nx + (uint32_t)(__popcll(bx1) + __popcll(bx2)) > room) {
             if (xq) fdel = false;
             x2 = false;
             bx1 = bx2 = 0;
@@ -660,9 +666,9 @@ __device__ __forceinline__ void dense_tile(const DenseArgs &d, const Win &v, con
             }
         }
         if (bx1) {
-            if (xq) queue[qcap - 1u - nx - mbcnt(bx1)] = j;
+            if (xq) queue[xslot(nx + mbcnt(bx1))] = j;
             nx += (uint32_t)__popcll(bx1);
-            if (x2) queue[qcap - 1u - nx - mbcnt(bx2)] = j + 2u;
+            if (x2) queue[xslot(nx + mbcnt(bx2))] = j + 2u;
             nx += (uint32_t)__popcll(bx2);
         }
         // the rest: the general walk; '-' runs and SEQ N / '-' straight into the byte counters
@@ -679,6 +685,63 @@ __device__ __forceinline__ void dense_tile(const DenseArgs &d, const Win &v, con
                             if (kd == S2C_RUN_BASES && (kind & S2C_RUN_XBIT))
                                 x_events(bxl, bql, rq, rl, r0, TL, (kind & S2C_RUN_DROP) != 0, dcnt, ncnt, ccnt);
                         });
+        }
+    };
+    if constexpr (EXT) {
+        // the 'N' events of the one-token reads (the host's list: tile-relative positions
+        // inside the tile's words), then thread i on rare piece i of the window's list
+        if (!ABL(4)) {
+            if (tid < xw.nnev) cnt_add1(ncnt, Pc[1].x);
+            for (uint32_t i = tid + WT; i < xw.nnev; i += WT) cnt_add1(ncnt, d.dnev[xw.nev0 + i]);
+        }
+        PROF_MARK(2);
+        for (uint32_t base = 0; base < (ABL(16) ? 0u : xw.nrare); base += WT) {
+            const uint32_t i = base + tid;
+            const bool on = i < xw.nrare;
+            uint3 R = Pc[0];
+            if (base) R = on ? ((const uint3 *)d.drare)[xw.rare0 + i] : make_uint3(0u, 0u, 0u);   // (windows of more than WT rare pieces)
+            rare_piece(on, R.x, R.y, R.z, 0xFFFFFFFFu);
+        }
+    } else {
+#pragma unroll
+        for (int u = 0; u < PFN; u++)
+            if ((uint32_t)u < nit) lean(tid + WT * u, Pc[u]);
+        for (uint32_t it = PFN; it < nit; it++) {   // (windows of more than WT·PFN pieces)
+            const uint32_t k = tid + WT * it;
+            lean(k, k < npc ? dpc_load(d, v.dpc0 + k) : make_uint3(0u, 0u, 0u));
+        }
+        // (the queued work below is this wave's own — its queue, its pieces' run records, atomic
+        // byte-counter adds — so its LDS writes completing is enough: the other wave's records are
+        // needed only by the count, after the barrier that ends the queued walks)
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        PROF_MARK(2);
+        // queued pieces, one per lane and round.  A piece's record comes from the lane that loaded
+        // it (ds_bpermute, all lanes on).
+        for (uint32_t base = 0; base < (ABL(16) ? 0u : nslow); base += WGD) {
+            const uint32_t i = base + lane;
+            const bool on = i < nslow;
+            const uint32_t k = on ? queue[i] : 0u, it = k / WT;
+            const int src = (int)(4 * (k % WGD));   // (k ≡ this wave's lane mod 64: WT is a multiple of 64)
+            uint32_t c0 = 0, c1 = 0, pxv = 0;
+#pragma unroll
+            for (int u = 0; u < PFN; u++) {
+                const uint32_t px = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)Pc[u].x);
+                const uint32_t py = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)Pc[u].y);
+                const uint32_t pz = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)Pc[u].z);
+                const bool me = it == (uint32_t)u;
+                c0 = me ? px : c0;
+                c1 = me ? py : c1;
+                pxv = me ? pz : pxv;
+            }
+            if (on && it >= (uint32_t)PFN) {   // (windows of more than WT·PFN pieces)
+                const uint3 R = dpc_load(d, v.dpc0 + k);
+                c0 = R.x;
+                c1 = R.y;
+                pxv = R.z;
+            }
+            // (front entries [base + 64, nslow) are still to be read: the back stays above nslow
+            // until the last round, which has read every front entry)
+            rare_piece(on, c0, c1, pxv, qcap - (base + WGD < nslow ? nslow : 0u));
         }
     }
     lds_sync();   // every run record written
@@ -853,8 +916,14 @@ __device__ __forceinline__ void dense_tile(const DenseArgs &d, const Win &v, con
     PROF_MARK(5);
     // queued single-token runs of reads with N / '-' in SEQ (never dropped: maxdel is off; 0.08
     // per C5 wave: read here, where their registers are not live through the count)
+    if constexpr (EXT) {   // (the one-token reads' X runs: the host's list of their slots)
+        for (uint32_t i = tid; i < (ABL(32) ? 0u : xw.nxs); i += WT) {
+            const Rec rc = rec_dec(runl[d.dxs[xw.xs0 + i]]);
+            x_events(bxl, bql, rc.q, rc.l, rc.r0, TL, false, dcnt, ncnt, ccnt);
+        }
+    }
     for (uint32_t i = lane; i < (ABL(32) ? 0u : nx); i += WGD) {
-        const Rec rc = rec_dec(runl[queue[qcap - 1u - i]]);
+        const Rec rc = rec_dec(runl[queue[xslot(i)]]);
         x_events(bxl, bql, rc.q, rc.l, rc.r0, TL, false, dcnt, ncnt, ccnt);
     }
     lds_sync();   // the byte counters are final, and every wave's count is done: the window's LDS is scratch
@@ -1150,7 +1219,7 @@ __device__ __forceinline__ void dense_tile(const DenseArgs &d, const Win &v, con
         atomicAdd(&g_prof[9], (unsigned long long)ngrp);
         atomicAdd(&g_prof[10], (unsigned long long)npc);
         atomicAdd(&g_prof[11], (unsigned long long)(v.nslot + 3 * v.nqw));
-        atomicAdd(&g_prof[12], (unsigned long long)nslow);
+        atomicAdd(&g_prof[12], (unsigned long long)(EXT ? xw.nrare : nslow));
         atomicAdd(&g_prof[13], (unsigned long long)nx);
     }
 #endif
@@ -1159,7 +1228,7 @@ __device__ __forceinline__ void dense_tile(const DenseArgs &d, const Win &v, con
 // One wave per tile (block b → item, XCD-major: the blocks of one XCD, b ≡ x mod 8, take a
 // contiguous range of items, so neighbouring windows meet in that XCD's L2).  Everything the
 // tile needs arrives by one LDS-DMA round trip after the scalar loads of its tile record.
-template <int NWP>
+template <int NWP, bool EXT>
 __global__ __launch_bounds__(WT) void k_tile_dense(const DenseArgs d) {
     extern __shared__ uint4 arena[];   // the window (S2C_DENSE_BYTES layout)
     // one byte per position (row layout): '-' (D/N/P runs, '-' of SEQ unless maxdel drops
@@ -1182,9 +1251,10 @@ __global__ __launch_bounds__(WT) void k_tile_dense(const DenseArgs d) {
     const uint32_t tid = threadIdx.x, b = blockIdx.x;
     const uint32_t x = b & 7u, per = d.n_items >> 3, rem = d.n_items & 7u;
     const uint32_t item = x * per + min(x, rem) + (b >> 3);
-    const Win v = win_of(d, item);
+    XWin xw;
+    const Win v = win_of<EXT>(d, item, xw);
     uint8_t *const buf = (uint8_t *)arena;
-    win_issue<WPT>(d, v, buf);
+    win_issue<WPT, EXT>(d, v, xw, buf);
     const WinLds wl = win_lds(d, v, buf);
     if (tid < RUN_PAD) wl.runl[v.nslot + tid] = make_uint2(0u, 0u);   // (the DMA does not write there)
     // with the DMA: the thread's piece records and its word's run-slot range
@@ -1194,7 +1264,14 @@ __global__ __launch_bounds__(WT) void k_tile_dense(const DenseArgs d) {
     for (int i = 0; i < PFN; i++) {
         const uint32_t k = tid + WT * i;
         Pc[i] = make_uint3(0u, 0u, 0u);
-        if (k < v.npc) Pc[i] = dpc_load(d, v.dpc0 + k);
+        if constexpr (!EXT) {
+            if (k < v.npc) Pc[i] = dpc_load(d, v.dpc0 + k);
+        }
+    }
+    if constexpr (EXT) {   // (dense_tile: the thread's rare record and its 'N' event; the rest in its loops)
+        static_assert(PFN >= 2, "Pc[1] holds the 'N' event");
+        if (tid < xw.nrare) Pc[0] = ((const uint3 *)d.drare)[xw.rare0 + tid];
+        if (tid < xw.nnev) Pc[1].x = d.dnev[xw.nev0 + tid];
     }
     const uint32_t w = (tid >> 6) * (NWP / WPT) + (tid & 63) / G, W = v.W0 + w, K = d.kwin;
     uint32_t cw0 = 0, cw1 = 0;
@@ -1223,13 +1300,14 @@ __global__ __launch_bounds__(WT) void k_tile_dense(const DenseArgs d) {
     cw0 -= v.o0;
     cw1 -= v.o0;
     lds_sync();
-    dense_tile<NWP>(d, v, wl, dcnt, ncnt, ccnt, amb, fill0, Pc, cw0, cw1, t_entry, stl, threadIdx.x, buf);
+    dense_tile<NWP, EXT>(d, v, xw, wl, dcnt, ncnt, ccnt, amb, fill0, Pc, cw0, cw1, t_entry, stl, threadIdx.x, buf);
 }
 
 
 template <int NWP>
-int launch(const DenseArgs &a, int64_t n, hipStream_t s) {
-    k_tile_dense<NWP><<<(unsigned)n, WT, a.buf_bytes, s>>>(a);
+int launch(const DenseArgs &a, bool ext, int64_t n, hipStream_t s) {
+    if (ext) k_tile_dense<NWP, true><<<(unsigned)n, WT, a.buf_bytes, s>>>(a);
+    else k_tile_dense<NWP, false><<<(unsigned)n, WT, a.buf_bytes, s>>>(a);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? S2C_OK : s2c_set_error(S2C_ERR_HIP, std::string("k_tile_dense: ") + hipGetErrorString(e));
 }
@@ -1251,13 +1329,17 @@ extern "C" int s2c_prof_dense(unsigned long long *out, int reset) {
 }
 #endif
 
-int s2c_launch_dense(const s2c_dev *dv, hipStream_t st) {
+int s2c_launch_dense(const s2c_dev *dv, const s2c_dense_ext *ext, hipStream_t st) {
     using namespace s2c;
     if (dv->n_dense <= 0) return S2C_OK;
     if (dv->fill_len != 1) return s2c_set_error(S2C_ERR_ARG, "dense tiles need a one-char fill");
     if (dv->n_dense >= ((int64_t)1 << 31)) return s2c_set_error(S2C_ERR_LIMIT, "too many dense tiles");
     DenseArgs a;
-    if (!dv->dpc || !dv->dwin) return s2c_set_error(S2C_ERR_ARG, "dense tiles need dwin and dpc (ABI 12)");
+    // (with the windows' extension — checked by the caller, s2c_pileup_ext — dpc is not read)
+    if ((!ext && !dv->dpc) || !dv->dwin) return s2c_set_error(S2C_ERR_ARG, "dense tiles need dwin and dpc (ABI 12)");
+    a.drun = ext ? ext->drun : nullptr; a.dnev = ext ? ext->dnev : nullptr; a.dxs = ext ? ext->dxs : nullptr;
+    a.drare = ext ? ext->drare : nullptr; a.dext = ext ? ext->dext : nullptr;
+    a.drun_end = ext ? ext->drun + 2 * ext->n_drun : nullptr;
     a.rs = dv->rs; a.lp = dv->lp; a.pc = dv->pc; a.dwin = dv->dwin; a.dpc = dv->dpc; a.ops = dv->ops; a.bq = dv->bq; a.bx = dv->bx; a.tiles = dv->tiles; a.items = dv->dense;
     a.thresholds = dv->thresholds; a.tile_stats = dv->tile_stats; a.blk_len = dv->blk_len; a.out = dv->out;
     a.padded_len = (uint32_t)dv->padded_len; a.n_cols = (uint32_t)dv->n_cols; a.n_tiles = (uint32_t)dv->n_tiles;
@@ -1279,8 +1361,8 @@ int s2c_launch_dense(const s2c_dev *dv, hipStream_t st) {
     static_assert(WPT * XCH_WAVE_BYTES == S2C_DENSE_MIN_LDS, "s2c.h S2C_DENSE_MIN_LDS (the host's occupancy plan)");
     a.buf_bytes = (uint32_t)std::max<int64_t>(lds + (WPT > 2 ? 256 * WPT : 0), (int64_t)WPT * XCH_WAVE_BYTES);
     if constexpr (WPT <= 2) {   // (≥ 8 words per wave)
-        if (dv->tile_max <= 512) return launch<16>(a, n, st);
+        if (dv->tile_max <= 512) return launch<16>(a, ext != nullptr, n, st);
     }
-    if (dv->tile_max <= 1024) return launch<32>(a, n, st);
-    return launch<64>(a, n, st);   // tile_max ≤ 2048 (host plan)
+    if (dv->tile_max <= 1024) return launch<32>(a, ext != nullptr, n, st);
+    return launch<64>(a, ext != nullptr, n, st);   // tile_max ≤ 2048 (host plan)
 }

@@ -339,6 +339,10 @@ struct s2c_batch {
     u32buf px;           // [pieces] the non-ACGT SEQ offsets of S2C_PF_XFEW pieces (s2c.h)
     std::vector<uint32_t> dwin;   // [dense][S2C_DWIN_WORDS] the dense items' windows (s2c.h)
     u32buf dpc;                   // [n_dpc][S2C_DPC_WORDS] compact piece records of the dense windows (s2c.h)
+    // the dense windows' extension (s2c.h s2c_dense_ext; build_dwin): run records, 'N' events,
+    // X-run slots, the rare pieces' records, and each window's {first, count} in the four
+    u32buf drun, dnev, dxs, drare, dext;   // (each written whole by build_dwin)
+    int64_t n_drun = 0, n_dnev = 0, n_dxs = 0, n_drare = 0;   // records / entries
 };
 
 inline int perr(s2c_parser *p, int code, const std::string &msg) {

@@ -98,20 +98,93 @@ void build_dwin(s2c_batch *b) {
     b->info.n_dpc = (int64_t)base[nd];
     b->dpc.resize(std::max<uint64_t>(base[nd], 1) * S2C_DPC_WORDS);
     if (!base[nd]) b->dpc[0] = b->dpc[1] = b->dpc[2] = 0;
-    par_ranges(plan_threads((int64_t)nd, 64), (int64_t)nd, [&](int, int64_t i0, int64_t i1) {
+    // The extension (s2c.h s2c_dense_ext) in two passes over the windows: each window's counts
+    // {'N' events, X-run slots, rare pieces} into its dext row, a prefix sum, then the entries
+    // with the compact records.  What a piece adds — one for both passes:
+    //   ev(r)   an 'N' event of a SIMPLE | XFEW piece at tile-relative position r
+    //   xs()    a SIMPLE piece whose non-ACGT chars are read from the planes
+    //   rare()  a piece neither SIMPLE nor LONG
+    auto classify = [](uint32_t fl, uint32_t rs, uint32_t slen, uint32_t px, uint32_t TL, auto &&ev, auto &&xs, auto &&rare) {
+        if (fl & S2C_PF_SIMPLE) {
+            if (fl & S2C_PF_XFEW) {
+                for (int u = 0; u < 2; u++) {
+                    const uint32_t off = (px >> (16 * u)) & 0xFFFFu, r = rs + off - 2048u;   // (r < 0 wraps past TL)
+                    if (off < slen && r < TL) ev(r);
+                }
+            } else if (fl & S2C_PF_X) {
+                xs();
+            }
+        } else if (!(fl & S2C_PF_LONG)) {
+            rare();
+        }
+    };
+    b->dext.resize(std::max<size_t>(nd, 1) * S2C_DEXT_WORDS);
+    if (!nd) std::fill(b->dext.begin(), b->dext.end(), 0u);
+    const int nth = plan_threads((int64_t)nd, 64);
+    par_ranges(nth, (int64_t)nd, [&](int, int64_t i0, int64_t i1) {
         for (int64_t i = i0; i < i1; i++) {
             const uint32_t *w = &b->dwin[(size_t)i * S2C_DWIN_WORDS];
-            const uint32_t T0 = 32 * (w[1] >> 5), o0 = w[8], qw0 = w[10];
+            const uint32_t T0 = 32 * (w[1] >> 5), TL = 32 * ((w[2] - w[1] + 31) / 32);
+            uint32_t nev = 0, nxs = 0, nrare = 0;
+            for (uint32_t k = w[6]; k < w[7]; k++) {
+                const uint32_t *pc = &b->pc[4 * (size_t)k];
+                classify(pc[3] >> 24, pc[0] - T0 + 2048u, pc[3] & 0xFFFFFFu, b->px[k], TL, [&](uint32_t) { nev++; },
+                         [&] { nxs++; }, [&] { nrare++; });
+            }
+            uint32_t *x = &b->dext[(size_t)i * S2C_DEXT_WORDS];
+            x[1] = w[9] - w[8];
+            x[3] = nev;
+            x[5] = nxs;
+            x[7] = nrare;
+        }
+    });
+    uint64_t tot[4] = {0, 0, 0, 0};   // records of drun (each block from an even record: 16 bytes), dnev, dxs, drare
+    for (size_t i = 0; i < nd; i++) {
+        uint32_t *x = &b->dext[i * S2C_DEXT_WORDS];
+        for (int c = 0; c < 4; c++) {
+            x[2 * c] = (uint32_t)tot[c];
+            tot[c] += c == 0 ? (x[1] + 1u) & ~1u : x[2 * c + 1];
+        }
+        if (tot[0] >= ((uint64_t)1 << 31)) throw std::runtime_error("more than 2^31 dense window run records");
+    }
+    b->n_drun = (int64_t)tot[0];
+    b->n_dnev = (int64_t)tot[1];
+    b->n_dxs = (int64_t)tot[2];
+    b->n_drare = (int64_t)tot[3];
+    b->drun.resize(std::max<uint64_t>(tot[0], 2) * 2);
+    b->dnev.resize(std::max<uint64_t>(tot[1], 1));
+    b->dxs.resize(std::max<uint64_t>(tot[2], 1));
+    b->drare.resize(std::max<uint64_t>(tot[3], 1) * S2C_DPC_WORDS);
+    if (!tot[0]) std::fill(b->drun.begin(), b->drun.end(), 0u);
+    if (!tot[1]) b->dnev[0] = 0;
+    if (!tot[2]) b->dxs[0] = 0;
+    if (!tot[3]) b->drare[0] = b->drare[1] = b->drare[2] = 0;
+    par_ranges(nth, (int64_t)nd, [&](int, int64_t i0, int64_t i1) {
+        for (int64_t i = i0; i < i1; i++) {
+            const uint32_t *w = &b->dwin[(size_t)i * S2C_DWIN_WORDS];
+            const uint32_t T0 = 32 * (w[1] >> 5), o0 = w[8], qw0 = w[10], TL = 32 * ((w[2] - w[1] + 31) / 32);
+            const uint32_t *x = &b->dext[(size_t)i * S2C_DEXT_WORDS];
             uint32_t *o = &b->dpc[base[i] * S2C_DPC_WORDS];
+            uint32_t *run = &b->drun[2 * (size_t)x[0]], *nev = &b->dnev[x[2]], *xs = &b->dxs[x[4]];
+            uint32_t *rare = &b->drare[(size_t)x[6] * S2C_DPC_WORDS];
+            std::fill(run, run + 2 * (size_t)((x[1] + 1u) & ~1u), 0u);   // (every slot but the SIMPLE pieces')
             for (uint32_t k = w[6]; k < w[7]; k++, o += S2C_DPC_WORDS) {
                 const uint32_t *pc = &b->pc[4 * (size_t)k];
                 const uint32_t rs = pc[0] - T0 + 2048u, qh = pc[1] - 2 * qw0, nops = pc[6] - pc[2], oj = pc[2] - o0;
-                const uint32_t slen = pc[3] & 0xFFFFFFu;
+                const uint32_t slen = pc[3] & 0xFFFFFFu, fl = pc[3] >> 24;
                 if (rs >= 4096u || qh >= 8192u || nops > S2C_DPC_NOPS_MAX || oj >= 8192u || slen > S2C_DPC_SLEN_MAX)
                     throw std::runtime_error("dense window piece beyond the compact record's fields");
                 o[0] = rs | qh << 12 | nops << 25;
-                o[1] = oj | slen << 13 | (pc[3] >> 24) << 24;
+                o[1] = oj | slen << 13 | fl << 24;
                 o[2] = b->px[k];
+                if (fl & S2C_PF_SIMPLE) {   // the run k_tile_dense's lean walk writes (rec_enc_b)
+                    run[2 * oj] = rs | (rs + slen) << 16;
+                    run[2 * oj + 1] = 16u * qh - rs;
+                }
+                classify(fl, rs, slen, o[2], TL, [&](uint32_t r) { *nev++ = r; }, [&] { *xs++ = oj; },
+                         [&] {
+                             for (int c = 0; c < S2C_DPC_WORDS; c++) *rare++ = o[c];
+                         });
             }
         }
     });

@@ -225,6 +225,21 @@ extern "C" int s2c_batch_arrays_get(const s2c_batch *b, s2c_batch_arrays *o) {
     return S2C_OK;
 }
 
+extern "C" int s2c_batch_dense_ext_get(const s2c_batch *b, s2c_dense_ext *o) {
+    if (!b || !o) return s2c_set_error(S2C_ERR_ARG, "NULL argument");
+    o->drun = b->drun.data();
+    o->dnev = b->dnev.data();
+    o->dxs = b->dxs.data();
+    o->drare = b->drare.data();
+    o->dext = b->dext.data();
+    o->n_drun = b->n_drun;
+    o->n_dnev = b->n_dnev;
+    o->n_dxs = b->n_dxs;
+    o->n_drare = b->n_drare;
+    o->n_dext = b->info.n_dense;
+    return S2C_OK;
+}
+
 extern "C" const char *s2c_batch_ref_name(const s2c_batch *b, int64_t i) {
     if (!b || i < 0 || i >= (int64_t)b->names.size()) return nullptr;
     return b->names[i].c_str();

@@ -27,7 +27,7 @@
 #include "s2c_common.h"
 
 int s2c_launch_reads(const s2c_dev *d, hipStream_t s, bool all, bool run);
-int s2c_launch_dense(const s2c_dev *d, hipStream_t s);
+int s2c_launch_dense(const s2c_dev *d, const s2c_dense_ext *ext, hipStream_t s);
 
 #ifdef S2C_PROF
 // phase clocks of k_tile (diagnostic build `make prof`, scripts/prof_tile.py): Σ over sampled
@@ -2092,7 +2092,23 @@ extern "C" int s2c_reads(const s2c_dev *d, void *stream) {
     return s2c_launch_reads(d, (hipStream_t)stream, false, true);
 }
 
-extern "C" int s2c_pileup(const s2c_dev *d, void *stream) {
+// the dense windows' extension of s2c_pileup_ext / s2c_run_ext (s2c.h), after check_dev
+static int check_ext(const s2c_dev *d, const s2c_dense_ext *x) {
+    if (!x) return S2C_OK;
+    const struct { const uint32_t *p; int64_t n; const char *name; } a[5] = {
+        {x->drun, x->n_drun, "drun"}, {x->dnev, x->n_dnev, "dnev"}, {x->dxs, x->n_dxs, "dxs"}, {x->drare, x->n_drare, "drare"},
+        {x->dext, x->n_dext, "dext"}};
+    for (const auto &e : a) {
+        if (e.n < 0 || e.n >= ((int64_t)1 << 31)) return s2c_set_error(S2C_ERR_ARG, std::string("s2c_dense_ext: bad count of ") + e.name);
+        if (e.n > 0 && !e.p) return s2c_set_error(S2C_ERR_ARG, std::string("s2c_dense_ext: ") + e.name + " is NULL with a non-zero count");
+    }
+    // (a window's block of drun goes to LDS by 16-byte DMA with no phase: s2c.h's even first record)
+    if ((uintptr_t)x->drun & 15) return s2c_set_error(S2C_ERR_ARG, "s2c_dense_ext: drun is not 16-byte aligned");
+    if (x->n_dext != d->n_dense) return s2c_set_error(S2C_ERR_ARG, "s2c_dense_ext: n_dext differs from s2c_dev.n_dense");
+    return S2C_OK;
+}
+
+extern "C" int s2c_pileup_ext(const s2c_dev *d, const s2c_dense_ext *ext, void *stream) {
     int rc = check_dev(d);
     if (rc) return rc;
     // dense tiles emit exactly one char per position: len(fill) must be 1, else k_tile (which
@@ -2100,16 +2116,18 @@ extern "C" int s2c_pileup(const s2c_dev *d, void *stream) {
     if (d->n_dense > 0 && d->fill_len != 1 && !d->layers_dense)
         return s2c_set_error(S2C_ERR_ARG, "a fill of length != 1 runs the dense tiles through k_tile: their layered "
                                           "windows are needed (s2c_batch_layers_mode(b, 1))");
+    if ((rc = check_ext(d, ext))) return rc;
     hipStream_t s = (hipStream_t)stream;
     const TileArgs a = tile_args(*d);
     // (the deep tiles' HBM counts are zero: before the first run by the caller, after every
     // run by s2c_consensus — s2c_dev.counts)
     if (d->n_dense > 0) {
-        rc = d->fill_len == 1 ? s2c_launch_dense(d, s) : launch_tiles(a, d->tile_max, d->dense, d->n_dense, s);
+        rc = d->fill_len == 1 ? s2c_launch_dense(d, ext, s) : launch_tiles(a, d->tile_max, d->dense, d->n_dense, s);
         if (rc) return rc;
     }
     return launch_tiles(a, d->tile_max, d->items, d->n_items, s);
 }
+extern "C" int s2c_pileup(const s2c_dev *d, void *stream) { return s2c_pileup_ext(d, nullptr, stream); }
 
 extern "C" int s2c_consensus(const s2c_dev *d, void *stream) {
     int rc = check_dev(d);
@@ -2121,12 +2139,14 @@ extern "C" int s2c_consensus(const s2c_dev *d, void *stream) {
     return S2C_OK;
 }
 
-extern "C" int s2c_run(const s2c_dev *d, void *stream) {
+extern "C" int s2c_run_ext(const s2c_dev *d, const s2c_dense_ext *ext, void *stream) {
     int rc;
+    if ((rc = check_dev(d)) || (rc = check_ext(d, ext))) return rc;   // (a bad extension: before s2c_reads launches)
     if ((rc = s2c_reads(d, stream))) return rc;
-    if ((rc = s2c_pileup(d, stream))) return rc;
+    if ((rc = s2c_pileup_ext(d, ext, stream))) return rc;
     return s2c_consensus(d, stream);
 }
+extern "C" int s2c_run(const s2c_dev *d, void *stream) { return s2c_run_ext(d, nullptr, stream); }
 
 extern "C" int s2c_pileup_counts(const s2c_dev *d, void *stream) {
     int rc = check_dev(d);

@@ -8,6 +8,10 @@ from . import _lib as L
 # the packed batch's device arrays, in upload order (s2c_dev's pointer fields)
 ARRAYS = ("pc", "ops", "bq", "bx", "rs", "tiles", "items", "dense", "deep", "lp", "wtile", "rlist", "ps",
           "lly", "lpc", "lops", "lbq", "lbx", "px", "dwin", "lpx", "dpc")
+# the dense windows' extension (s2c_dense_ext), uploaded in place of dpc: with it k_tile_dense
+# does not read the compact records (UPLOAD: what a run through the _ext entries uploads)
+EXT_ARRAYS = ("drun", "dnev", "dxs", "drare", "dext")
+UPLOAD = tuple(n for n in ARRAYS if n != "dpc") + EXT_ARRAYS
 # the workspace buffers a run writes (s2c_workspace_sizes), plus the thresholds and fill
 BUFFERS = ("runs", "ibkt", "ilong", "ilong_n", "counts", "ins_cols", "ins_chr", "tile_stats", "blk_len", "out")
 
@@ -18,7 +22,7 @@ def fill_dev(info, arrays, bufs, n_thr, min_depth, fill, maxdel_active, maxdel, 
     i = info
     d = L.Dev()
     for name in ARRAYS:
-        setattr(d, name, arrays[name])
+        setattr(d, name, arrays.get(name))   # (dpc: None, i.e. NULL, when the extension replaces it)
     d.n_pieces, d.n_ops, d.n_qwords, d.n_tiles = i.n_pieces, i.n_ops, i.n_qwords, i.n_tiles
     d.n_items, d.n_dense, d.n_deep = i.n_items, i.n_dense, i.n_deep
     d.padded_len, d.chunk, d.kwin, d.tile_max = i.padded_len, i.chunk, i.kwin, i.tile_max
@@ -39,3 +43,14 @@ def fill_dev(info, arrays, bufs, n_thr, min_depth, fill, maxdel_active, maxdel, 
     d.n_cols = i.n_cols
     d.out_cap = int(out_cap)
     return d
+
+
+def fill_ext(hb, arrays, n_dense=None):
+    """The ``s2c_dense_ext`` of a run: ``arrays``: name → device address of each of EXT_ARRAYS
+    (the batch ``hb``'s, whole); ``n_dense``: dext's rows when they were filtered like dwin."""
+    x = L.DenseExt()
+    for name in EXT_ARRAYS:
+        setattr(x, name, arrays[name])
+    x.n_drun, x.n_dnev, x.n_dxs, x.n_drare = len(hb.drun), len(hb.dnev), len(hb.dxs), len(hb.drare)
+    x.n_dext = len(hb.dext) if n_dense is None else int(n_dense)
+    return x

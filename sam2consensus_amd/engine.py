@@ -15,7 +15,7 @@ import torch
 
 from . import _lib as L
 from ._lib import lib
-from .devargs import ARRAYS, fill_dev
+from .devargs import EXT_ARRAYS, UPLOAD, fill_dev, fill_ext
 
 
 def _dev(device):
@@ -188,7 +188,7 @@ class DeviceBatch:
     default for batches of 64 MB or more) the arrays go through its pinned staging ring and
     copy stream (asynchronous); otherwise each array is copied synchronously."""
 
-    ARRAYS = ARRAYS   # (devargs: s2c_dev's pointer fields, in upload order)
+    ARRAYS = UPLOAD   # (devargs: s2c_dev's pointer fields less dpc, and the dense windows' extension, in upload order)
 
     def __init__(self, hb, device=None, uploader=None, dense_layers=False):
         self.device = _dev(device) if uploader is None else uploader.device
@@ -283,6 +283,12 @@ class Workspace:
             d.n_dense = int(len(keep(hb.dense, 0)))
             d.n_deep = int(((hb.deep >= t0) & (hb.deep < t1)).sum())
         self.dev = d
+        # the dense windows' extension (s2c_run_ext / s2c_pileup_ext): its rows filtered like dwin
+        self.ext = fill_ext(db.hb, {name: getattr(db, name).data_ptr() for name in EXT_ARRAYS})
+        if tile_range is not None:
+            sel = (db.hb.dwin[:, 0] >= t0) & (db.hb.dwin[:, 0] < t1) if len(db.hb.dwin) else np.zeros(0, dtype=bool)
+            self._sel["dext"] = _up(np.ascontiguousarray(db.hb.dext[sel]).reshape(-1), dev)
+            self.ext.dext, self.ext.n_dext = _ptr(self._sel["dext"]), int(sel.sum())
 
     def stream_handle(self):
         return C.c_void_p(torch.cuda.current_stream(self.db.device).cuda_stream)
@@ -299,7 +305,7 @@ class Workspace:
 
     def pileup(self):
         self._counts_ready()
-        L.check(lib.s2c_pileup(C.byref(self.dev), self.stream_handle()))
+        L.check(lib.s2c_pileup_ext(C.byref(self.dev), C.byref(self.ext), self.stream_handle()))
 
     def consensus(self):
         self._tables_held = False   # (k_consensus clears the deep tiles' insertion tables)
@@ -309,7 +315,7 @@ class Workspace:
         """reads → pileup (+ insertion columns, vote, FASTA bodies) → deep tiles (no host sync)."""
         self._counts_ready()
         self._tables_held = False
-        L.check(lib.s2c_run(C.byref(self.dev), self.stream_handle()))
+        L.check(lib.s2c_run_ext(C.byref(self.dev), C.byref(self.ext), self.stream_handle()))
 
     def record_done(self):
         """An event after this workspace's launches so far on the compute stream: ``fetch(done)``

@@ -22,7 +22,7 @@ import numpy as np
 
 from . import _lib as L
 from ._lib import lib
-from .devargs import ARRAYS, BUFFERS, fill_dev
+from .devargs import BUFFERS, EXT_ARRAYS, UPLOAD, fill_dev, fill_ext
 
 ALIGN = 256
 _H2D, _D2H = 1, 2                       # hipMemcpyHostToDevice, hipMemcpyDeviceToHost
@@ -160,7 +160,7 @@ class Session:
         t0 = time.perf_counter()
         hb.ensure_layers(len(fill) != 1)   # (engine.needs_dense_layers: a fill of length != 1)
         i = type(hb.info).from_buffer_copy(hb.info)
-        arrays = [np.ascontiguousarray(np.asarray(hb.device_view(n)).reshape(-1)).view(np.uint8) for n in ARRAYS]
+        arrays = [np.ascontiguousarray(np.asarray(hb.device_view(n)).reshape(-1)).view(np.uint8) for n in UPLOAD]
         offs, total = _layout([a.nbytes for a in arrays])
         self._grow(total)
         host = self._staging(total)
@@ -193,10 +193,12 @@ class Session:
             fb = np.frombuffer(fill or b"\0", dtype=np.uint8)
             hip.memcpy(bufs["thresholds"], thr.ctypes.data, thr.nbytes, _H2D)
             hip.memcpy(bufs["fill"], fb.ctypes.data, fb.nbytes, _H2D)
-            d = fill_dev(i, {n: self.dbuf + o for n, o in zip(ARRAYS, offs)}, bufs, T, min_depth, fill,
+            addr = {n: self.dbuf + o for n, o in zip(UPLOAD, offs)}
+            d = fill_dev(i, addr, bufs, T, min_depth, fill,
                          getattr(hb, "maxdel_active", True), getattr(hb, "maxdel", 150), cap)
+            x = fill_ext(hb, {n: addr[n] for n in EXT_ARRAYS})
             t3 = time.perf_counter()
-            L.check(lib.s2c_run(C.byref(d), C.c_void_p()))
+            L.check(lib.s2c_run_ext(C.byref(d), C.byref(x), C.c_void_p()))
             hip.sync()
             t4 = time.perf_counter()
             res = self._fetch(hb, i, T, fill_w, cap, bufs)

@@ -2,10 +2,16 @@
 
     python scripts/bound.py <workload> <pmc dir, e.g. gpurun_out/pmc_c5> <evidence path>
 Per launch of the tile kernels (k_tile_dense, k_tile, k_prep), summed: the VALU issue floor
-(SQ_INSTS_VALU × 4 clocks per wave64 instruction on one of 1024 SIMDs at 2.4 GHz,
-MI355X_MICROARCH.md) and the HBM floor (profiles/traffic_<wl>.json bytes ÷ 8 TB/s), each as
-a fraction of the kernels' time under the counters.  The larger one is the bound; writes
-profiles/bound_<wl>.json, which bench.py reports as roofline.bound."""
+(SQ_INSTS_VALU × 2 clocks per wave64 instruction on one of 1024 SIMDs at 2.4 GHz: a CDNA4
+SIMD is 32 lanes wide and issues a wave64 VALU instruction over 2 cycles — the MI355X
+microarchitecture guide, rows `v_fma_f32` and "vector-instruction ISSUE cost"; 4 is what one
+wave alone sustains, not what a SIMD with several waves does) and the HBM floor
+(profiles/traffic_<wl>.json bytes ÷ 8 TB/s), each as a fraction of the kernels' time under the
+counters.  The larger one is the bound when it reaches half of that time; when neither does,
+the kernels run well short of both limits and the bound is "latency" (the waves' lifetime: waits
+and issue of every kind).  Where a pass holds SQ_ACTIVE_INST_VALU (or SQ_BUSY_CYCLES) it is
+reported per VALU instruction beside the price used.  Writes profiles/bound_<wl>.json, which
+bench.py reports as roofline.bound."""
 import csv
 import glob
 import json
@@ -15,11 +21,12 @@ from collections import defaultdict
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TILE = ("s2c::k_tile_dense", "s2c::k_tile", "s2c::k_prep")
+VALU_CLOCKS = 2   # per wave64 VALU instruction on a SIMD-32 (see above)
 
 
 def main():
     wl, base, evidence = sys.argv[1], sys.argv[2], sys.argv[3]
-    valu, dur = defaultdict(list), defaultdict(list)
+    valu, dur, active = defaultdict(list), defaultdict(list), defaultdict(list)
     for f in glob.glob(os.path.join(base, "**", "*counter_collection.csv"), recursive=True):
         with open(f) as fh:
             for row in csv.DictReader(fh):
@@ -29,9 +36,12 @@ def main():
                 if row["Counter_Name"] == "SQ_INSTS_VALU":
                     valu[name].append(float(row["Counter_Value"]))
                     dur[name].append((int(row["End_Timestamp"]) - int(row["Start_Timestamp"])) * 1e-6)
+                if row["Counter_Name"] == "SQ_ACTIVE_INST_VALU":
+                    active[name].append(float(row["Counter_Value"]))
     v = sum(sum(x) / len(x) for x in valu.values())
     t = sum(sum(x) / len(x) for x in dur.values())
-    valu_ms = v * 4 / 1024 / 2.4e9 * 1e3
+    valu_ms = v * VALU_CLOCKS / 1024 / 2.4e9 * 1e3
+    act = sum(sum(x) / len(x) for x in active.values()) if active else None
     tr = None
     p = os.path.join(ROOT, "profiles", "traffic_%s.json" % wl)
     if os.path.exists(p):
@@ -40,7 +50,10 @@ def main():
     fv = valu_ms / t if t else None
     fh = hbm_ms / t if (t and hbm_ms) else None
     bound = "valu" if (fv and (fh is None or fv >= fh)) else "hbm"
+    if max(fv or 0.0, fh or 0.0) < 0.5:
+        bound = "latency"
     out = {"workload": wl, "bound": bound, "kernels": sorted(valu), "valu_insts_per_launch": v,
+           "valu_clocks_per_inst": VALU_CLOCKS, "valu_active_counter_per_inst": (act / v if (act and v) else None),
            "valu_floor_ms": valu_ms, "hbm_floor_ms": hbm_ms, "kernel_ms_under_counters": t,
            "valu_frac_of_time": fv, "hbm_frac_of_time": fh, "evidence": evidence}
     json.dump(out, open(os.path.join(ROOT, "profiles", "bound_%s.json" % wl), "w"), indent=1)

@@ -2,8 +2,8 @@
 
     python scripts/pmc_summary.py gpurun_out/pmc_c3 [kernel-substring]
 Prints one line per (kernel, counter); SQ_INSTS_* are per dispatch (all waves), and the
-derived VALU cycles assume one wave64 VALU instruction per SIMD quad-cycle (4 clocks) on
-1024 SIMDs at 2.4 GHz (MI355X_MICROARCH.md)."""
+derived VALU floor prices a wave64 VALU instruction at 2 clocks (a SIMD-32 issues it over 2
+cycles: scripts/bound.py) on 1024 SIMDs at 2.4 GHz."""
 import csv
 import glob
 import os
@@ -28,7 +28,7 @@ def main():
         m = sum(v) / len(v)
         extra = ""
         if c == "SQ_INSTS_VALU":
-            extra = "  (VALU floor %.3f ms)" % (m * 4 / 1024 / 2.4e9 * 1e3)
+            extra = "  (VALU floor %.3f ms)" % (m * 2 / 1024 / 2.4e9 * 1e3)
         print("%-40s %-24s %16.1f  (n=%d)%s" % (k[:40], c, m, len(v), extra))
     for k, v in sorted(dur.items()):
         print("%-40s duration under counters %.3f ms" % (k[:40], sum(v) / len(v)))
