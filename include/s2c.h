@@ -32,8 +32,10 @@
  *              the run records of the rare long pieces;
  *          (4) k_consensus: tiles whose depth or insertion layout exceeds one workgroup;
  *          (5) the tables as text, formatted where the counts and the insertion events are:
- *              k_table_* (--counts), k_sites_* (--variants), k_runs_* (--depth, --lowcov) and
- *              k_ins_* (--insertions: the motifs of (3) grouped, ordered and printed per tile).
+ *              k_table_* (--counts), k_sites_* (--variants), k_runs_* (--depth, --lowcov),
+ *              k_ins_* (--insertions: the motifs of (3) grouped, ordered and printed per tile) and
+ *              k_links_* (--links: one more walk of every piece, against the mask of the mixed
+ *              sites, counts the symbol pairs fragments carry across neighbouring sites).
  */
 #ifndef S2C_H
 #define S2C_H
@@ -673,6 +675,46 @@ int s2c_ins_write(const uint32_t *tiles, int64_t n_tiles, int64_t n_bkt, int64_t
                   const uint32_t *bx, int64_t n_qwords, const uint32_t *counts, int64_t padded_len,
                   const int64_t *blocks, const uint32_t *scratch, const int64_t *offs, uint8_t *dst, int64_t dst_len,
                   void *stream);
+
+/* Allele pairs across neighbouring mixed sites as text (the CLI's --links; csrc/s2c_links.hip).
+ * The sites are the set bits of a mask as s2c_sites_mark writes it; the rank of a site is the
+ * number of set bits below it, and site k pairs with site k + 1.  A fragment is a piece of the
+ * batch; it observes symbol s at position p iff it adds one to counts[s][p] (:210-218): a '-' of
+ * a read over maxdel is no observation.  pairs = u32 [n_sites][6][6], 16-byte aligned:
+ * pairs[k][s1][s2] the fragments that observe s1 at site k and s2 at site k + 1 with no
+ * observed site between (a site whose '-' was dropped links nothing across it).
+ *   s2c_links_pop    pop[w] = popcount(mask[w]) for the ⌈padded_len / 64⌉ mask words (u32).  The
+ *                    caller's exclusive prefix sum is rank[w], the set bits below word w, and the
+ *                    sum of all of them n_sites (< 2^32).
+ *   s2c_links_count  walks every piece (pc, ops, bq, bx of n_pieces pieces and n_qwords plane
+ *                    words, as s2c_dev's; maxdel_active / maxdel as s2c_dev's) and ADDS to pairs,
+ *                    which the caller zeroed.  It reads no run record and no piece list.  A run
+ *                    is clamped to padded_len, a base outside the planes is no observation, and
+ *                    a rank at or past n_sites adds nothing, so a test can pass a mask, rank and
+ *                    pairs it built itself.  Integer adds: the result does not depend on order.
+ *   s2c_links_len, s2c_links_write   the two passes of the other tables over the count tables'
+ *                    blocks {a, b, p0} and the run tables' refs {s, e}, valid as s2c_runs_len's.
+ *                    A pair belongs to the block that holds its first site g1; its second site
+ *                    g2 is the next set bit, possibly several blocks on, and must be < e.  With
+ *                    READS = Σ pairs[k] (64-bit) and HAPS its non-zero entries the pair is listed
+ *                    iff READS >= min_reads (1 <= min_reads < 2^32): the line
+ *                    "P1\tP2\tREADS\tHAPS\tXY:n,XY:n,...\n", P = p0 + (g − a), X and Y the
+ *                    characters of s1 and s2, the non-zero entries by n falling, then by (s1, s2)
+ *                    in S2C_NSYM order — a total order; at most 542 bytes (READS up to 12 digits).
+ *                    lens[i] = the exact bytes of block i's lines, 0 for a block outside the
+ *                    bounds; s2c_links_write writes them to dst[offs[i], offs[i+1]) and no byte
+ *                    outside it, skipping the blocks s2c_sites_write skips.
+ * Every loop is bounded by a checked length.  All four are asynchronous on stream and allocate
+ * nothing; they add no struct field (ABI 14 stands). */
+int s2c_links_pop(const uint64_t *mask, int64_t padded_len, uint32_t *pop, void *stream);
+int s2c_links_count(const uint32_t *pc, const uint32_t *ops, const uint32_t *bq, const uint32_t *bx, int64_t n_pieces,
+                    int64_t n_qwords, int maxdel_active, int maxdel, const uint64_t *mask, const uint32_t *rank,
+                    int64_t padded_len, int64_t n_sites, uint32_t *pairs, void *stream);
+int s2c_links_len(const uint64_t *mask, const uint32_t *rank, int64_t padded_len, const uint32_t *pairs, int64_t n_sites,
+                  const int64_t *blocks, const int64_t *refs, int64_t n, int64_t min_reads, int64_t *lens, void *stream);
+int s2c_links_write(const uint64_t *mask, const uint32_t *rank, int64_t padded_len, const uint32_t *pairs, int64_t n_sites,
+                    const int64_t *blocks, const int64_t *refs, const int64_t *offs, int64_t n, int64_t min_reads,
+                    uint8_t *dst, int64_t dst_len, void *stream);
 
 /* Diagnostics (tests only, not part of the product path): k_reads over every piece, then
  * every tile's counts stored to d->counts ([6][padded_len] u32) and no vote. */

@@ -131,6 +131,7 @@ EXPORTS = [
     "s2c_sites_mark", "s2c_sites_len", "s2c_sites_write",
     "s2c_runs_mark", "s2c_runs_len", "s2c_runs_write",
     "s2c_ins_len", "s2c_ins_write",
+    "s2c_links_pop", "s2c_links_count", "s2c_links_len", "s2c_links_write",
 ]
 
 
@@ -223,6 +224,12 @@ def _load():
                                   C.c_int64, _VP, _VP, _VP]),
         "s2c_ins_write": (C.c_int, [_VP, C.c_int64, C.c_int64, C.c_int64, _VP, _VP, C.c_int64, _VP, C.c_int64, _VP, _VP, _VP, _VP,
                                     C.c_int64, _VP]),
+        "s2c_links_pop": (C.c_int, [_VP, C.c_int64, _VP, _VP]),
+        "s2c_links_count": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int64, C.c_int64, C.c_int, C.c_int, _VP, _VP, C.c_int64, C.c_int64,
+                                      _VP, _VP]),
+        "s2c_links_len": (C.c_int, [_VP, _VP, C.c_int64, _VP, C.c_int64, _VP, _VP, C.c_int64, C.c_int64, _VP, _VP]),
+        "s2c_links_write": (C.c_int, [_VP, _VP, C.c_int64, _VP, C.c_int64, _VP, _VP, _VP, C.c_int64, C.c_int64, _VP, C.c_int64,
+                                      _VP]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)

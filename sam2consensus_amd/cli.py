@@ -79,21 +79,31 @@ def build_parser():
     p.add_argument("--min-ins-reads", action="store", dest="min_ins_reads", type=int, default=None, metavar="N",
                    help="With --insertions: list a motif only when at least N reads carry it, default=1")
     p.add_argument("--min-alt-reads", action="store", dest="min_alt_reads", type=int, default=None, metavar="N",
-                   help="With --variants: least number of reads not of the major symbol at a site, default=2")
+                   help="With --variants or --links: least number of reads not of the major symbol at a site, default=2")
     p.add_argument("--min-alt-frac", action="store", dest="min_alt_frac", type=float, default=None, metavar="F",
-                   help="With --variants: least share of the coverage not of the major symbol at a site, "
+                   help="With --variants or --links: least share of the coverage not of the major symbol at a site, "
                         "between 0 and 1, default=0.05")
+    p.add_argument("--links", action="store_true", dest="links", default=False,
+                   help="Also write REF__PREFIX.links.tsv beside each FASTA file: one line pos1, pos2, reads, haps, pairs "
+                        "(tab-separated) per pair of neighbouring --variants sites (same -m, --min-alt-reads and "
+                        "--min-alt-frac; --variants itself is not needed) that at least one read, or one part of a read "
+                        "around the POS <= 0 wrap, observes together: the two 1-based positions, the reads that carry a "
+                        "counted symbol at both, the number of distinct symbol pairs, and those pairs as XY:count with X "
+                        "and Y from -ACGNT, by count (falling), then by X and Y; independent of -c, -f and -n. "
+                        "Not available with more than one process or with S2C_STREAM")
+    p.add_argument("--min-link-reads", action="store", dest="min_link_reads", type=int, default=None, metavar="N",
+                   help="With --links: list a pair of sites only when at least N reads observe both, default=1")
     return p
 
 
 MIN_ALT_READS, MIN_ALT_FRAC = 2, 0.05
 
 
-def variants_of(parser, args):
-    """(min_alt, min_frac) of --variants or None; a bad value, or either option without
-    --variants, is the parser's error (exit status 2)."""
+def _site_rule(parser, args):
+    """(min_alt, min_frac) of the sites --variants lists and --links pairs, or None with neither
+    flag; a bad value, or either option with neither flag, is the parser's error (exit status 2)."""
     n, f = args.min_alt_reads, args.min_alt_frac
-    if not args.variants:
+    if not args.variants and not args.links:
         for opt, v in (("--min-alt-reads", n), ("--min-alt-frac", f)):
             if v is not None:
                 parser.error(opt + " needs --variants")
@@ -105,6 +115,29 @@ def variants_of(parser, args):
     if not 0.0 <= f <= 1.0:   # (a NaN too)
         parser.error("--min-alt-frac must be between 0 and 1")
     return n, f
+
+
+def variants_of(parser, args):
+    """(min_alt, min_frac) of --variants or None (the checks: ``_site_rule``)."""
+    rule = _site_rule(parser, args)
+    return rule if args.variants else None
+
+
+MIN_LINK_READS = 1
+
+
+def links_of(parser, args):
+    """(min_alt, min_frac, min_reads) of --links or None; --min-link-reads outside [1, 2^32) or
+    without --links is the parser's error (exit status 2)."""
+    n = args.min_link_reads
+    if not args.links:
+        if n is not None:
+            parser.error("--min-link-reads needs --links")
+        return None
+    n = MIN_LINK_READS if n is None else n
+    if not 1 <= n < 2 ** 32:
+        parser.error("--min-link-reads must be at least 1 and below 2^32")
+    return _site_rule(parser, args) + (n,)
 
 
 MIN_INS_READS = 1
@@ -140,7 +173,7 @@ class RunResult:
 
 
 def consensus_batch(hb, thresholds, prefix, min_depth=1, fill=b"-", nchar=0, device=None, timings=None,
-                    counts=False, variants=None, depth=False, lowcov=False, insertions=None):
+                    counts=False, variants=None, depth=False, lowcov=False, insertions=None, links=None):
     """Device pipeline on a parsed HostBatch → {``REF__PREFIX.fasta``: bytes}; with ``counts``
     also the ``REF__PREFIX.counts.tsv`` count tables (table.py), after the FASTA entries, and
     with ``variants`` = (min_alt, min_frac) the ``REF__PREFIX.variants.tsv`` tables of mixed
@@ -148,7 +181,8 @@ def consensus_batch(hb, thresholds, prefix, min_depth=1, fill=b"-", nchar=0, dev
     ``REF__PREFIX.depth.tsv`` intervals of equal coverage, with ``lowcov`` the
     ``REF__PREFIX.lowcov.tsv`` runs of coverage below max(min_depth, 1), and last, with
     ``depth``, the one ``PREFIX.depth_summary.tsv``; with ``insertions`` = min_reads the
-    ``REF__PREFIX.insertions.tsv`` insertion motif tables after all of those — the run then
+    ``REF__PREFIX.insertions.tsv`` insertion motif tables after all of those, and with ``links`` =
+    (min_alt, min_frac, min_reads) the ``REF__PREFIX.links.tsv`` link tables last — the run then
     takes the counts route (``Workspace.run_with_tables``)."""
     import torch
 
@@ -158,7 +192,7 @@ def consensus_batch(hb, thresholds, prefix, min_depth=1, fill=b"-", nchar=0, dev
     t = timings if timings is not None else {}
     t0 = time.perf_counter()
     runs = bool(depth) or bool(lowcov)
-    tables = bool(counts) or variants is not None or runs or insertions is not None
+    tables = bool(counts) or variants is not None or runs or insertions is not None or links is not None
     db = DeviceBatch(hb, device, dense_layers=needs_dense_layers(fill, tables))
     t1 = time.perf_counter()
     ws = Workspace(db, thresholds, min_depth, fill, keep_counts=tables)
@@ -173,8 +207,11 @@ def consensus_batch(hb, thresholds, prefix, min_depth=1, fill=b"-", nchar=0, dev
         sites = (max(int(min_depth), 1),) + tuple(variants) if variants is not None else None
         least = max(int(min_depth), 1)
         res = ws.run_with_tables(counts=bool(counts), sites=sites, depth=least if depth else None,
-                                 lowcov=least if lowcov else None, insertions=insertions)
-        # (counts, sites[, depth, lowcov][, insertions]: run_with_tables' docstring)
+                                 lowcov=least if lowcov else None, insertions=insertions,
+                                 links=(least,) + tuple(links) if links is not None else None)
+        # (counts, sites[, depth, lowcov][, insertions][, links]: run_with_tables' docstring)
+        ktab = res[-1] if links is not None else None
+        res = res[:-1] if links is not None else res
         itab = res[-1] if insertions is not None else None
         ctab, stab = res[:2]
         dtab, ltab = res[2:4] if runs else (None, None)
@@ -202,7 +239,8 @@ def consensus_batch(hb, thresholds, prefix, min_depth=1, fill=b"-", nchar=0, dev
                             (depth, text(dtab, tb.DEPTH_HEADER, tb.DEPTH_SUFFIX)),
                             (lowcov, text(ltab, tb.LOWCOV_HEADER, tb.LOWCOV_SUFFIX)),
                             (depth, lambda: tb.summary_file(hb, pre, dtab[2])),
-                            (insertions is not None, text(itab, tb.INS_HEADER, tb.INS_SUFFIX))):
+                            (insertions is not None, text(itab, tb.INS_HEADER, tb.INS_SUFFIX)),
+                            (links is not None, text(ktab, tb.LINKS_HEADER, tb.LINKS_SUFFIX))):
             if asked:
                 files.update(make())
     t["format"] = time.perf_counter() - t0
@@ -315,7 +353,7 @@ def consensus_batch_hip(sess, hb, thresholds, prefix, min_depth=1, fill=b"-", nc
 
 
 def _consensus_files_tables(filename, thresholds, prefix, min_depth, fill, nchar, maxdel_active, device, log,
-                            counts, variants, depth=False, lowcov=False, insertions=None):
+                            counts, variants, depth=False, lowcov=False, insertions=None, links=None):
     """consensus_files with any of the tables: the torch engine path (consensus_batch)."""
     import torch
 
@@ -342,12 +380,13 @@ def _consensus_files_tables(filename, thresholds, prefix, min_depth, fill, nchar
     if log:
         _log_summary(log, hb.info)
     files = consensus_batch(hb, thresholds, prefix, min_depth, fill, nchar, dev, t, counts=counts, variants=variants,
-                            depth=depth, lowcov=lowcov, insertions=insertions)
+                            depth=depth, lowcov=lowcov, insertions=insertions, links=links)
     return RunResult(files, t, hb.info, hb.free_async())
 
 
 def consensus_files(filename, thresholds, prefix, min_depth=1, fill=b"-", nchar=0, maxdel_active=True,
-                    device=None, log=None, counts=False, variants=None, depth=False, lowcov=False, insertions=None):
+                    device=None, log=None, counts=False, variants=None, depth=False, lowcov=False, insertions=None,
+                    links=None):
     """Run the whole pipeline on one SAM/SAM.gz file; returns a RunResult whose
     ``files`` maps ``REF__PREFIX.fasta`` → content bytes (nothing written).  The device side
     runs through the HIP runtime directly (hiprun.py): this path never imports PyTorch.
@@ -355,10 +394,11 @@ def consensus_files(filename, thresholds, prefix, min_depth=1, fill=b"-", nchar=
     ``variants`` = (min_alt, min_frac) the ``REF__PREFIX.variants.tsv`` tables of mixed sites,
     with ``depth`` / ``lowcov`` the ``.depth.tsv`` / ``.lowcov.tsv`` runs of coverage (and the
     depth summary), with ``insertions`` = min_reads the ``.insertions.tsv`` insertion motif tables,
-    and the run goes through the torch engine path instead (``consensus_batch``)."""
-    if counts or variants is not None or depth or lowcov or insertions is not None:
+    with ``links`` = (min_alt, min_frac, min_reads) the ``.links.tsv`` link tables, and the run goes
+    through the torch engine path instead (``consensus_batch``)."""
+    if counts or variants is not None or depth or lowcov or insertions is not None or links is not None:
         return _consensus_files_tables(filename, thresholds, prefix, min_depth, fill, nchar, maxdel_active, device, log,
-                                       bool(counts), variants, bool(depth), bool(lowcov), insertions)
+                                       bool(counts), variants, bool(depth), bool(lowcov), insertions, links)
     from .batch import Parser
     from .hiprun import Session, device_index
 
@@ -390,20 +430,23 @@ def consensus_files(filename, thresholds, prefix, min_depth=1, fill=b"-", nchar=
     return RunResult(files, t, hb.info, hb.free_async())
 
 
-def run_text(sam_text, argv, device=None, counts=False, variants=None, depth=False, lowcov=False, insertions=None):
+def run_text(sam_text, argv, device=None, counts=False, variants=None, depth=False, lowcov=False, insertions=None,
+             links=None):
     """Library entry for tests: SAM text + CLI args (without -i) → (status, {fname: str}).
     status is "ok" or the reference's exception class name; nothing touches the disk.
     ``counts`` (or ``--counts`` among the args): the count tables too; ``variants`` =
     (min_alt, min_frac) (or ``--variants`` and its options among the args): the tables of
     mixed sites too; ``depth`` / ``lowcov`` (or ``--depth`` / ``--lowcov``): the depth intervals
     with their summary / the low-coverage runs too; ``insertions`` = min_reads (or ``--insertions``
-    and ``--min-ins-reads``): the insertion motif tables too."""
+    and ``--min-ins-reads``): the insertion motif tables too; ``links`` = (min_alt, min_frac,
+    min_reads) (or ``--links`` and its options): the link tables too."""
     from .batch import parse_text
 
     parser = build_parser()
     args = parser.parse_args(["-i", "in.sam"] + list(argv))
     variants = variants_of(parser, args) or variants
     insertions = insertions_of(parser, args) or insertions
+    links = links_of(parser, args) or links
     try:
         thresholds = [float(i) for i in args.thresholds.split(",")]
         prefix = args.prefix or "in"
@@ -411,7 +454,7 @@ def run_text(sam_text, argv, device=None, counts=False, variants=None, depth=Fal
         files = consensus_batch(hb, thresholds, os.fsencode(prefix), args.min_depth,
                                 os.fsencode(args.fill), args.n, device, counts=bool(counts or args.counts),
                                 variants=variants, depth=bool(depth or args.depth), lowcov=bool(lowcov or args.lowcov),
-                                insertions=insertions)
+                                insertions=insertions, links=links)
     except (KeyError, IndexError, ValueError, ZeroDivisionError, OverflowError) as e:
         return type(e).__name__, {}
     return "ok", {k.decode("latin-1"): v.decode("latin-1") for k, v in files.items()}
@@ -482,8 +525,9 @@ def main(argv=None):
     args = parser.parse_args(argv)
     variants = variants_of(parser, args)
     insertions = insertions_of(parser, args)
+    links = links_of(parser, args)
     for flag, on in (("--counts", args.counts), ("--variants", variants is not None), ("--depth", args.depth),
-                     ("--lowcov", args.lowcov), ("--insertions", insertions is not None)):
+                     ("--lowcov", args.lowcov), ("--insertions", insertions is not None), ("--links", links is not None)):
         if on:   # (refused before a folder is made or a device touched)
             if _dist_env()[0] > 1:
                 parser.error(flag + " is not available with more than one process (WORLD_SIZE > 1)")
@@ -520,7 +564,7 @@ def main(argv=None):
             res = consensus_files(filename, thresholds, os.fsencode(prefix), args.min_depth,
                                   os.fsencode(args.fill), args.n, maxdel_active, log=lambda s: print(s),
                                   counts=args.counts, variants=variants, depth=args.depth, lowcov=args.lowcov,
-                                  insertions=insertions)
+                                  insertions=insertions, links=links)
             files = res.files
     tables = []
     for fname, body in files.items():                                             # :411-424
@@ -534,6 +578,8 @@ def main(argv=None):
             tables.append("Depth table saved for " + os.fsdecode(fname[: fname.rfind(b"__")]) + " in: " + shown)
         elif insertions is not None and fname.endswith(b".insertions.tsv"):   # (last: after the depth summary)
             tables.append("Insertion table saved for " + os.fsdecode(fname[: fname.rfind(b"__")]) + " in: " + shown)
+        elif links is not None and fname.endswith(b".links.tsv"):   # (last of all: after the insertion tables)
+            tables.append("Link table saved for " + os.fsdecode(fname[: fname.rfind(b"__")]) + " in: " + shown)
         elif args.lowcov and fname.endswith(b".lowcov.tsv"):
             tables.append("Low-coverage table saved for " + os.fsdecode(fname[: fname.rfind(b"__")]) + " in: " + shown)
         elif args.counts and fname.endswith(b".counts.tsv"):

@@ -196,6 +196,14 @@ __device__ __forceinline__ void walk_piece(const Mem &m, const uint4 P, uint32_t
     }
 }
 
+struct GlobalMem {   // walk_piece's view of the batch in HBM (k_reads, k_links_count)
+    const uint32_t *ops, *bq, *bx;
+    __device__ __forceinline__ uint32_t op(uint32_t j) const { return ops[j]; }
+    __device__ __forceinline__ uint32_t p0(uint64_t w) const { return bq[2 * w]; }
+    __device__ __forceinline__ uint32_t p1(uint64_t w) const { return bq[2 * w + 1]; }
+    __device__ __forceinline__ uint32_t x(uint64_t w) const { return bx[w]; }
+};
+
 }  // namespace s2c
 
 extern "C" __device__ __attribute__((const)) unsigned long long __ockl_wfred_add_u64(unsigned long long);

@@ -299,22 +299,6 @@ __global__ __launch_bounds__(TWG) void k_ins_len(const InsArgs d, int64_t *__res
     }
 }
 
-// The tile's range of dst: no byte is stored outside [0, cap).  o[k] = ch is put(k, ch), so
-// put32 / put64 (s2c_text.h) write their digits through it.
-struct Out {
-    uint8_t *d;
-    uint64_t cap;
-    __device__ __forceinline__ void put(uint64_t o, uint32_t ch) const {
-        if (o < cap) d[o] = (uint8_t)ch;
-    }
-    struct Byte {
-        const Out &out;
-        uint64_t o;
-        __device__ __forceinline__ void operator=(uint8_t ch) const { out.put(o, ch); }
-    };
-    __device__ __forceinline__ Byte operator[](uint64_t o) const { return Byte{*this, o}; }
-};
-
 // tile i's lines → dst[offs[i], offs[i+1]); never a byte outside that range
 __global__ __launch_bounds__(TWG) void k_ins_write(const InsArgs d, const int64_t *__restrict__ offs,
                                                     uint8_t *__restrict__ dst, int64_t dst_len) {

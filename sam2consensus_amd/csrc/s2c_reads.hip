@@ -28,14 +28,6 @@ struct ReadsArgs {
     uint32_t skip_fin, kwin;                  // s2c_reads: events k_tile records are left to it (below)
 };
 
-struct GlobalMem {   // walk_piece's view of the batch in HBM
-    const uint32_t *ops, *bq, *bx;
-    __device__ __forceinline__ uint32_t op(uint32_t j) const { return ops[j]; }
-    __device__ __forceinline__ uint32_t p0(uint64_t w) const { return bq[2 * w]; }
-    __device__ __forceinline__ uint32_t p1(uint64_t w) const { return bq[2 * w + 1]; }
-    __device__ __forceinline__ uint32_t x(uint64_t w) const { return bx[w]; }
-};
-
 __device__ __forceinline__ uint64_t mix64(uint64_t k) {
     k ^= k >> 33;
     k *= 0xff51afd7ed558ccdULL;

@@ -64,17 +64,6 @@ __global__ __launch_bounds__(TWG) void k_runs_mark(const uint32_t *__restrict__ 
     }
 }
 
-// a block with the range [s, e) of its reference
-struct RBlk {
-    int64_t a, b, p0, s, e;
-    __device__ __forceinline__ bool ok(int64_t padded_len) const {
-        return s >= 0 && s <= a && a <= b && b <= e && e <= padded_len && p0 >= 0 && p0 <= TPOS_END - (e - a);
-    }
-};
-__device__ __forceinline__ RBlk load_rblk(const int64_t *__restrict__ blocks, const int64_t *__restrict__ refs, uint64_t i) {
-    return RBlk{blocks[3 * i], blocks[3 * i + 1], blocks[3 * i + 2], refs[2 * i], refs[2 * i + 1]};
-}
-
 // The first set bit of mask in [b, e), or e: the end of the run that holds position b − 1
 // (b < e).  The whole workgroup steps over the words, RLOOK per lane and step (their loads in
 // flight together): a ballot per word finds each wave's first non-zero one, the lowest

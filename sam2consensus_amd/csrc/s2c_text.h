@@ -1,5 +1,6 @@
 // s2c_text.h — the scheme of the kernels that write tables as text (s2c_table.hip, s2c_sites.hip,
-// s2c_runs.hip, s2c_ins.hip); each of those files keeps its line's format and what it selects.
+// s2c_runs.hip, s2c_ins.hip, s2c_links.hip); each of those files keeps its line's format and what
+// it selects.
 //
 // Lines have no fixed width, so a table takes two launches over its blocks {a, b, p0}, one
 // workgroup per block, grid-strided: a length pass (block_total: lens[i] = bytes of block i's
@@ -11,8 +12,9 @@
 // destination's misalignment, so LDS reads and global stores are both 16-byte aligned; head and
 // tail bytes go out singly.  A sparse table picks its lines by a mask of one bit per position
 // that a mark kernel left, and walk_mask queues a block's set bits for the two passes.
-// Also here: the decimal digit code, one position's row and its counts line, and the blocks
-// with their guards.
+// Also here: the decimal digit code, one position's row and its counts line, the blocks with
+// their guards (with their reference's range: RBlk), and the guarded byte writer (Out) of the
+// kernels whose lines are too long for the LDS image.
 #pragma once
 #include "s2c_common.h"
 
@@ -130,6 +132,33 @@ struct Blk {
 __device__ __forceinline__ Blk load_blk(const int64_t *__restrict__ blocks, uint64_t i) {
     return Blk{blocks[3 * i], blocks[3 * i + 1], blocks[3 * i + 2]};
 }
+
+// a block with the range [s, e) of its reference (the run tables, the link tables)
+struct RBlk {
+    int64_t a, b, p0, s, e;
+    __device__ __forceinline__ bool ok(int64_t padded_len) const {
+        return s >= 0 && s <= a && a <= b && b <= e && e <= padded_len && p0 >= 0 && p0 <= TPOS_END - (e - a);
+    }
+};
+__device__ __forceinline__ RBlk load_rblk(const int64_t *__restrict__ blocks, const int64_t *__restrict__ refs, uint64_t i) {
+    return RBlk{blocks[3 * i], blocks[3 * i + 1], blocks[3 * i + 2], refs[2 * i], refs[2 * i + 1]};
+}
+
+// A block's range of dst for a writer that stores byte by byte (s2c_ins.hip, s2c_links.hip): no byte is stored outside [0, cap).  o[k] = ch is put(k, ch), so
+// put32 / put64 write their digits through it.
+struct Out {
+    uint8_t *d;
+    uint64_t cap;
+    __device__ __forceinline__ void put(uint64_t o, uint32_t ch) const {
+        if (o < cap) d[o] = (uint8_t)ch;
+    }
+    struct Byte {
+        const Out &out;
+        uint64_t o;
+        __device__ __forceinline__ void operator=(uint8_t ch) const { out.put(o, ch); }
+    };
+    __device__ __forceinline__ Byte operator[](uint64_t o) const { return Byte{*this, o}; }
+};
 
 // buf[sh, sh + tot) → d[0, tot), sh = d's offset inside its 16-byte word: 16-byte stores (LDS
 // reads and global stores both aligned), head and tail bytes singly

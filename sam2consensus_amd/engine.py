@@ -437,13 +437,61 @@ class Workspace:
         Lp, buf = self.db.info.padded_len, {}
 
         def len_call(nt, blocks, lens, st):
-            c, mask = _ptr(self.counts), _ptr(buf.setdefault("mask", self._mask_words()))
-            L.check(lib.s2c_sites_mark(c, Lp, int(min_cov), int(min_alt), float(min_frac), mask, st))
-            L.check(lib.s2c_sites_len(c, Lp, mask, blocks, nt, lens, st))
+            buf["mask"] = self._site_mask(min_cov, min_alt, min_frac, st)
+            L.check(lib.s2c_sites_len(_ptr(self.counts), Lp, _ptr(buf["mask"]), blocks, nt, lens, st))
 
         def write_call(nt, blocks, offs, text, total, st):
             L.check(lib.s2c_sites_write(_ptr(self.counts), Lp, _ptr(buf["mask"]), blocks, offs, nt, text, total, st))
         return self._two_pass("sites_table", len_call, write_call)
+
+    def _site_mask(self, min_cov, min_alt, min_frac, st):
+        """The mask s2c_sites_mark leaves for a rule.  Inside ``run_with_tables`` a rule is marked
+        once: the site tables and the link tables of one rule share the mask."""
+        rule = (int(min_cov), int(min_alt), float(min_frac))
+        held = getattr(self, "_site_masks", None)
+        if held is not None and rule in held:
+            return held[rule]
+        mask = self._mask_words()
+        L.check(lib.s2c_sites_mark(_ptr(self.counts), self.db.info.padded_len, rule[0], rule[1], rule[2], _ptr(mask), st))
+        if held is not None:
+            held[rule] = mask
+        return mask
+
+    def links_table(self, min_cov=1, min_alt=2, min_frac=0.05, min_reads=1):
+        """The allele pairs that fragments carry across neighbouring mixed sites as the text of
+        the link tables (table.py; the sites of ``sites_table``'s rule, s2c_links_pop and the
+        prefix sum for their ranks, s2c_links_count over every piece of the batch into ``pairs``
+        — n_sites · 144 bytes, allocated and zeroed here on every call —, then s2c_links_len, the
+        prefix sum and s2c_links_write, on the current stream): the return shape and the
+        preconditions of ``counts_table`` — the lines of the pairs whose first site lies in tile
+        k at [offs[k], offs[k+1]).  ``min_reads`` >= 1: the least reads of a listed pair.  One
+        host read more than the other tables make: n_sites, four bytes, sizes ``pairs``."""
+        db, i, buf = self.db, self.db.info, {}
+        Lp = i.padded_len
+
+        def own_checks():
+            if not 1 <= int(min_reads) < 2 ** 32:
+                raise ValueError("links_table: 1 <= min_reads < 2^32")
+
+        def len_call(nt, blocks, lens, st):
+            mask = buf["mask"] = self._site_mask(min_cov, min_alt, min_frac, st)
+            nw = (int(Lp) + 63) // 64
+            pop = torch.empty(max(nw, 1), dtype=torch.int32, device=db.device)
+            rank = buf["rank"] = torch.zeros(nw + 1, dtype=torch.int32, device=db.device)
+            L.check(lib.s2c_links_pop(_ptr(mask), Lp, _ptr(pop), st))
+            torch.cumsum(pop[:nw], 0, dtype=torch.int32, out=rank[1:])
+            ns = buf["n_sites"] = int(rank[-1].item()) & 0xFFFFFFFF
+            pairs = buf["pairs"] = torch.zeros(max(144 * ns, 16), dtype=torch.uint8, device=db.device)
+            d = self.dev
+            L.check(lib.s2c_links_count(_ptr(db.pc), _ptr(db.ops), _ptr(db.bq), _ptr(db.bx), int(i.n_pieces), int(i.n_qwords),
+                                        int(d.maxdel_active), int(d.maxdel), _ptr(mask), _ptr(rank), Lp, ns, _ptr(pairs), st))
+            L.check(lib.s2c_links_len(_ptr(mask), _ptr(rank), Lp, _ptr(pairs), ns, blocks, _ptr(self._table_refs()), nt,
+                                      int(min_reads), lens, st))
+
+        def write_call(nt, blocks, offs, text, total, st):
+            L.check(lib.s2c_links_write(_ptr(buf["mask"]), _ptr(buf["rank"]), Lp, _ptr(buf["pairs"]), buf["n_sites"], blocks,
+                                        _ptr(self._table_refs()), offs, nt, int(min_reads), text, total, st))
+        return self._two_pass("links_table", len_call, write_call, own_checks)
 
     def _table_refs(self):
         """Device int64 [n_tiles][2] {s, e}: the global range of the reference each tile lies in
@@ -516,7 +564,7 @@ class Workspace:
                                       blocks, _ptr(buf["scratch"]), offs, text, total, st))
         return self._two_pass("insertions_table", len_call, write_call, own_checks, filled_by="accumulate")
 
-    def run_with_tables(self, counts=True, sites=None, *, depth=None, lowcov=None, insertions=None):
+    def run_with_tables(self, counts=True, sites=None, *, depth=None, lowcov=None, insertions=None, links=None):
         """``run()`` through the counts route, with any of the tables: every tile's counts
         stored (s2c_accumulate on zeroed counts, the insertion tables kept), formatted as text
         (before the vote, which leaves the counts zero), then every tile voted from them
@@ -527,7 +575,9 @@ class Workspace:
         min_cov) or ``lowcov`` = cut (the runs of coverage < cut), two more:
         (..., depth_table(0, depth) or None, depth_table(lowcov) or None).  With ``insertions`` =
         min_reads one more element, last: insertions_table(insertions) — formatted before the
-        vote consumes the insertion tables."""
+        vote consumes the insertion tables.  With ``links`` = (min_cov, min_alt, min_frac,
+        min_reads) one more, after that: links_table(*links); a rule that ``sites`` has too is
+        marked once."""
         if not self.keep_counts:
             raise ValueError("run_with_tables needs Workspace(keep_counts=True)")
         if lowcov is not None and int(lowcov) < 1:
@@ -536,14 +586,20 @@ class Workspace:
         # (set first: if a stage raises, a reused workspace zeroes its counts before its next run)
         self._counts_filled = True
         self.accumulate(keep_tables=True)
-        table = self.counts_table() if counts else None
-        stable = self.sites_table(*sites) if sites is not None else None
-        dtable = self.depth_table(0, depth) if depth is not None else None
-        ltable = self.depth_table(lowcov) if lowcov is not None else None
-        itable = self.insertions_table(insertions) if insertions is not None else None
+        self._site_masks = {}
+        try:
+            table = self.counts_table() if counts else None
+            stable = self.sites_table(*sites) if sites is not None else None
+            dtable = self.depth_table(0, depth) if depth is not None else None
+            ltable = self.depth_table(lowcov) if lowcov is not None else None
+            itable = self.insertions_table(insertions) if insertions is not None else None
+            ktable = self.links_table(*links) if links is not None else None
+        finally:
+            self._site_masks = None
         self.vote_all()
         res = (table, stable) if depth is None and lowcov is None else (table, stable, dtable, ltable)
-        return res if insertions is None else res + (itable,)
+        res = res if insertions is None else res + (itable,)
+        return res if links is None else res + (ktable,)
 
     def run_with_counts(self):
         """``run_with_tables`` with the count tables alone.  Returns counts_table()'s (offs,

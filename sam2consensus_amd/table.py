@@ -38,6 +38,21 @@ carrying exactly this motif, its length and its characters from ``-ACGNT``.  Lin
 by ``pos``, then ``reads`` falling, ``len`` rising, then the motif symbol by symbol in
 ``-ACGNT`` order.  The device groups, orders and formats (csrc/s2c_ins.hip,
 ``Workspace.insertions_table``); ``format_insertions`` is the model.
+
+Link tables (``--links``): ``REF__PREFIX.links.tsv``, one line ``pos1\tpos2\treads\thaps\tpairs``
+per pair of neighbouring mixed sites that at least one read fragment observes together.  The
+sites are the positions ``--variants`` lists under the same ``-m``, ``--min-alt-reads`` and
+``--min-alt-frac``.  A fragment is a read, or each of the two parts of a read around the
+``POS <= 0`` wrap (:212's negative index).  It observes symbol ``s`` at position ``p`` iff it
+adds one to ``counts[s][p]`` (:210-218): a ``-`` of a read over ``-d`` is no observation, ``N``
+is a symbol like the others, and the observations of all fragments sum to the count table.  For
+sites ``p1 < p2`` of one reference with no site between them ``n[s1][s2]`` is the number of
+fragments that observe ``s1`` at ``p1`` and ``s2`` at ``p2``; a fragment that passes a site
+without observing it (its ``-`` dropped) links nothing across it.  ``reads`` = Σ n, ``haps`` the
+number of non-zero ``n[s1][s2]``, ``pairs`` those entries as ``XY:count`` joined by ``,``, by
+count falling, then by ``(s1, s2)`` in ``-ACGNT`` order — a total order.  A pair is listed iff
+``reads >= --min-link-reads`` (>= 1).  The device walks the reads and formats (csrc/s2c_links.hip,
+``Workspace.links_table``); ``link_pairs`` and ``format_links`` are the model.
 """
 from __future__ import annotations
 
@@ -57,6 +72,8 @@ SUMMARY_SUFFIX = b".depth_summary.tsv"
 EMPTY_STATS = (0, 0, 0, 0, 2 ** 63 - 1, -1)   # a block without a run start (s2c_runs_len)
 INS_HEADER = b"pos\tcov\treads\tlen\tmotif\n"
 INS_SUFFIX = b".insertions.tsv"
+LINKS_HEADER = b"pos1\tpos2\treads\thaps\tpairs\n"
+LINKS_SUFFIX = b".links.tsv"
 
 
 def format_rows(counts_6xL, p0=1):
@@ -119,6 +136,45 @@ def format_insertions(entries, cov, p0=1, min_reads=1):
     rows.sort(key=lambda r: r[:4])
     return "".join("%d\t%d\t%d\t%d\t%s\n" % (int(p0) + pos, int(cov[pos]), -nr, n, motif)
                    for pos, nr, n, _, motif in rows).encode("ascii")
+
+
+def link_pairs(fragments, site_positions):
+    """{k: n[6][6]} of the pairs (site k, site k + 1) that a fragment observes together.
+    ``fragments``: one list per fragment of its observations ``(pos, sym)`` in rising position,
+    ``sym`` an index into ``-ACGNT`` or the character; ``site_positions``: the sites of the
+    fragments' reference, rising.  Only an observation at site k followed, as the fragment's
+    next observation at a site, by one at site k + 1 counts."""
+    rank = {int(p): k for k, p in enumerate(site_positions)}
+    pairs = {}
+    for obs in fragments:
+        prev = None
+        for pos, sym in obs:
+            k = rank.get(int(pos))
+            if k is None:
+                continue
+            s = SYMBOLS.index(sym) if isinstance(sym, str) else int(sym)
+            if prev is not None and prev[0] + 1 == k:
+                pairs.setdefault(prev[0], [[0] * 6 for _ in range(6)])[prev[1]][s] += 1
+            prev = (k, s)
+    return pairs
+
+
+def format_links(pairs, site_positions, p0=1, min_reads=1):
+    """The link lines (no header) of ``pairs`` = {k: n[6][6]} over the sites ``site_positions``
+    (0-based, rising; position ``p0`` is printed for index 0): the pairs with ``reads >=
+    min_reads`` (>= 1) in site order."""
+    if int(min_reads) < 1:
+        raise ValueError("min_reads must be at least 1")
+    out = []
+    for k in sorted(pairs):
+        e = [(int(pairs[k][a][b]), a, b) for a in range(6) for b in range(6) if int(pairs[k][a][b])]
+        reads = sum(n for n, _, _ in e)
+        if reads < int(min_reads):
+            continue
+        e.sort(key=lambda x: (-x[0], x[1], x[2]))
+        out.append("%d\t%d\t%d\t%d\t%s\n" % (int(p0) + int(site_positions[k]), int(p0) + int(site_positions[k + 1]), reads, len(e),
+                                             ",".join("%s%s:%d" % (SYMBOLS[a], SYMBOLS[b], n) for n, a, b in e)))
+    return "".join(out).encode("ascii")
 
 
 def table_files(hb, prefix, offs, body, header=HEADER, suffix=SUFFIX):
