@@ -120,7 +120,7 @@ int s2c_layout(int64_t *out, int n);
 
 /* tile record tiles[t][S2C_TILE_WORDS] */
 #define S2C_TILE_WORDS   24  /* {a, b, ref, flags, boff, bcap, loff, lcap, cb0, ccap, lp0, lp1, nev,
-                                 pf0, pf1, o0, o1, qw0, qw1, nl, ly0, 0, 0, 0}: the window's pieces
+                                 pf0, pf1, o0, o1, qw0, qw1, nl, ly0, nit, 0, 0}: the window's pieces
                                  [pf0, pf1) (short pieces starting in [a/32 - kwin, b/32)), their op
                                  slots [o0, o1) and base plane words [qw0, qw1); nl LAYERS of the
                                  window, copied for k_tile as layers ly0 .. ly0 + nl - 1 of the
@@ -128,7 +128,9 @@ int s2c_layout(int64_t *out, int n);
                                  window, its short pieces [ps[s] + n_s*l/nl, ps[s] + n_s*(l+1)/nl)
                                  (n_s = ps[s+1] - ps[s]), in start-word order — one LDS chunk of
                                  k_tile (S2C_CHUNK_*); ly0 = S2C_LY_MAIN: one layer, the window read in
-                                 place from the sorted arrays (pf0 .. qw1) */
+                                 place from the sorted arrays (pf0 .. qw1); nit: the tile's work items
+                                 (item c counts entries [n*c/nit, n*(c+1)/nit) of its long list of n;
+                                 0 in a record built by hand: the first item counts them all) */
 #define S2C_LY_MAIN 0xFFFFFFFFu
 #define S2C_LY_NONE 0xFFFFFFFEu   /* a dense tile whose layered windows were not built (s2c_batch_layers_mode) */
 #define S2C_TILE_DEEP     1  /* several work items: counts summed in HBM, voted by k_consensus */
@@ -168,7 +170,7 @@ int s2c_layout(int64_t *out, int n);
    {p0, p1} through the word after its last base (funnel shift) and non-ACGT words — caps
    per layer — and its run records (= op slots), per 32-position word and counting lane <=
    S2C_CHUNK_LANE_RECS * lanes per word of a wave, 64 / words per tile (8-bit counters).  A work item's run records per
-   word are <= S2C_ITEM_RECS (its u16 histogram). */
+   word, its share of the tile's long list included, are <= S2C_ITEM_RECS (its u16 histogram). */
 #define S2C_CHUNK_PIECES     128
 #define S2C_CHUNK_QBYTES    4096
 /* a layer's base-plane bytes in k_tile<nwp, wq> (nwp: the tile's 32-position words, wq: the

@@ -565,10 +565,7 @@ void build_layers(s2c_batch *b, int64_t G, bool with_dense) {
     par_ranges(nt, (int64_t)NTL, [&](int, int64_t k0, int64_t k1) { copy_tiles((size_t)k0, (size_t)k1); });
 }
 
-// Work items of a tile of nl layers: {tile, c, l0, l1}, enough that each one's run records
-// per word stay <= S2C_ITEM_RECS (its u16 histogram) and, past 2·IL layers, an item takes
-// <= IL (parallelism for the deep tiles: C4's 16.5 kb at 100,000x); IL = 64 per-wave layers
-// (16 per wave), S2C_ITEM_LAYERS overrides.
+// Layers per work item of a deep tile: IL = 64 per-wave layers (16 per wave), S2C_ITEM_LAYERS overrides.
 static int64_t item_layers() {
     static const int64_t il = [] {
         const char *e = plan_env("S2C_ITEM_LAYERS");
@@ -576,23 +573,38 @@ static int64_t item_layers() {
     }();
     return il;
 }
-static int64_t plan_items(const s2c_batch *b, int64_t K, uint64_t a, uint64_t e, int64_t nl, int64_t IL) {
-    if (nl <= 1) return 1;   // (one layer: one item whatever its records)
+// Work items of a tile of nl layers: {tile, c, l0, l1}, enough that each one's run records
+// per word stay <= S2C_ITEM_RECS (its u16 histogram) and, past 2·IL layers, an item takes
+// <= IL (parallelism for the deep tiles: C4's 16.5 kb at 100,000x).
+// The bound covers everything an item adds to a position's u16 halves: per word W, the run
+// records of its layers' short pieces starting in words W - K .. W, and its share of the tile's
+// long list (item c of nch counts entries [nlg·c/nch, nlg·(c+1)/nch)) — at most its entries, and
+// at most the long pieces over W (lw[W]), since a piece's runs cover a position once.  A tile
+// whose long runs alone pass the bound gets more items than layers (the later ones' layer
+// ranges are empty) and so becomes deep.  0: no count of items keeps the bound (an error, not
+// reached: an item of one layer and one long-list entry holds <= S2C_CHUNK_RECS + 1).
+static int64_t plan_items(const s2c_batch *b, const PieceBlocks &B, int64_t K, uint64_t a, uint64_t e, int64_t nl, int64_t IL,
+                          int64_t nlg, const uint32_t *lw) {
+    if (nl <= 1 && nlg == 0) return 1;   // (one layer and no long run: its records fit the chunk)
     const int64_t W0 = (int64_t)(a >> 5), W1 = (int64_t)((e + 31) >> 5), S0 = std::max<int64_t>(W0 - K, 0);
     std::vector<LayerSeg> seg;
     for (int64_t s = S0; s < W1; s++) seg.push_back({b->ps[s], (uint64_t)(b->ps[s + 1] - b->ps[s]), (uint64_t)s});
     std::vector<uint64_t> cuts;
     tile_cuts(seg, (uint64_t)nl, cuts);
-    // op slot of each cut (the records between two cuts: their difference)
-    for (uint64_t &c : cuts) c = b->pc[4 * c + 2];
+    // the short pieces' op slots before each cut (the records between two cuts: their difference)
+    for (uint64_t &c : cuts) c = B.o[c];
     const uint64_t stride = (uint64_t)nl + 1;
+    const int64_t nmax = std::max(nl, nlg);
     int64_t nch = nl > 2 * IL ? (nl + IL - 1) / IL : 1;
+    if (nlg > S2C_ITEM_RECS && *std::max_element(lw + W0, lw + W1) > S2C_ITEM_RECS)   // (the share alone must fit)
+        nch = std::max<int64_t>(nch, (nlg + S2C_ITEM_RECS - 1) / S2C_ITEM_RECS);
     for (;; nch++) {
+        const int64_t lshare = (nlg + nch - 1) / nch;
         bool ok = true;
         for (int64_t c = 0; c < nch && ok; c++) {
             const uint64_t l0 = (uint64_t)(c * nl / nch), l1 = (uint64_t)((c + 1) * nl / nch);
             for (int64_t W = W0; W < W1 && ok; W++) {
-                int64_t r = 0;
+                int64_t r = std::min<int64_t>(lshare, lw[W]);
                 for (int64_t s = std::max(W - K, S0); s <= W; s++) {
                     const uint64_t *cs = &cuts[(uint64_t)(s - S0) * stride];
                     r += (uint32_t)(cs[l1] - cs[l0]);
@@ -600,7 +612,8 @@ static int64_t plan_items(const s2c_batch *b, int64_t K, uint64_t a, uint64_t e,
                 ok = r <= S2C_ITEM_RECS;
             }
         }
-        if (ok || nch >= nl) return nch;
+        if (ok) return nch;
+        if (nch >= nmax) return 0;
     }
 }
 
@@ -636,6 +649,7 @@ struct BatchPlan {
     int64_t dense_cap = S2C_DENSE_LDS;
     int64_t NT = 0;
     std::vector<uint32_t> lcnt;                      // long-list CSR by tile
+    std::vector<uint32_t> lwords;                    // long pieces over each word (plan_items' bound)
     std::vector<uint32_t> nshort, nlong, nev;        // per tile: insertion events by motif class, and all
     std::vector<uint64_t> ccap;                      // per tile: Σ motif lengths
     int64_t nwp = 8, G = 8, lcols = 0;               // k_tile<nwp>; counting lanes per word; its LDS columns
@@ -1177,6 +1191,13 @@ void BatchPlan::long_lists() {
         });
     }
     I.n_long = lcnt[NT];
+    lwords.assign(NW + 1, 0);
+    for (const int64_t k : longs) {   // (a difference array over the words, then its prefix sums)
+        const Piece &q = pcs[order[k]];
+        lwords[q.gpos >> 5]++;
+        lwords[((q.gpos + (q.kb - q.ka) - 1) >> 5) + 1]--;
+    }
+    for (int64_t W = 0; W < NW; W++) lwords[W + 1] += lwords[W];
 }
 
 // ---- insertion plan: per tile its events' hash-table capacity, long-motif slots and an
@@ -1213,7 +1234,7 @@ int BatchPlan::tile_plans() {
     t_nch.assign(NT, 0);
     t_maxc.assign(NT, 0);
     t_wruns.assign(NT, 0);
-    std::atomic<bool> too_big{false};
+    std::atomic<bool> too_big{false}, over_u16{false};
     const int64_t q0 = std::min(P0, NT), q1 = std::min(P1, NT);   // the planned tiles, in balanced ranges
     par_ranges(plan_threads(q1 - q0, 64), q1 - q0, [&](int, int64_t i0, int64_t i1) {
         for (int64_t t = q0 + i0; t < q0 + i1; t++) {
@@ -1227,11 +1248,13 @@ int BatchPlan::tile_plans() {
             const int64_t nl = plan_layers(b, PB, K, (uint64_t)T.a, (uint64_t)T.b, G, wq);
             t_nl[t] = nl;
             if (nl <= 0) { too_big = true; continue; }
-            t_nch[t] = plan_items(b, K, (uint64_t)T.a, (uint64_t)T.b, nl, item_layers());
+            t_nch[t] = plan_items(b, PB, K, (uint64_t)T.a, (uint64_t)T.b, nl, item_layers(), nlg, lwords.data());
+            if (t_nch[t] <= 0) { over_u16 = true; continue; }
             t_wruns[t] = (int64_t)b->rs[w1] - (int64_t)b->rs[std::max<int64_t>(w0 - K, 0)];
             tile_window(b, K, T.a, T.b, &b->tiles[(size_t)t * S2C_TILE_WORDS]);
         }
     });
+    if (over_u16) return s2c_set_error(S2C_ERR_LIMIT, "a tile's run records exceed its work items' u16 histograms");
     return too_big ? s2c_set_error(S2C_ERR_LIMIT, "a read whose SEQ or CIGAR exceeds k_tile's LDS chunk") : S2C_OK;
 }
 
@@ -1272,8 +1295,8 @@ void BatchPlan::shape_item_grid() {
             par_ranges(plan_threads(q1 - q0, 64), q1 - q0, [&](int, int64_t i0, int64_t i1) {
                 for (int64_t t = q0 + i0; t < q0 + i1; t++)
                     if (t_nch[t] > 1)
-                        t_nch[t] = std::max<int64_t>(t_nch[t], plan_items(b, K, (uint64_t)tiles[t].a, (uint64_t)tiles[t].b,
-                                                                          t_nl[t], best));
+                        t_nch[t] = std::max<int64_t>(t_nch[t], plan_items(b, PB, K, (uint64_t)tiles[t].a, (uint64_t)tiles[t].b, t_nl[t], best,
+                                                                          (int64_t)lcnt[t + 1] - lcnt[t], lwords.data()));
             });
     }
 }
@@ -1300,6 +1323,7 @@ int BatchPlan::tile_records() {
         tw[8] = (uint32_t)coff; tw[9] = (uint32_t)ccap[t]; tw[10] = lcnt[t]; tw[11] = lcnt[t + 1];
         tw[12] = nev[t];
         tw[19] = (uint32_t)nl;
+        tw[21] = planned(t) ? (uint32_t)nch : 0u;
         boff += bcap;
         loff += nlong[t];
         coff += ccap[t];

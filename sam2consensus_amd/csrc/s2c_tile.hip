@@ -1611,7 +1611,9 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(NWP <= 16 ? 
     constexpr uint32_t G = WG / NWP;
     const uint32_t w = tid / G, g = tid % G, W = W0 + w;
     const bool active = w < nwords;
-    // ---- long pieces (rare), counted once per tile (by its first item), one list entry per
+    // ---- long pieces (rare), counted once per tile (item c of the tile's nit, tile word 21,
+    //      takes entries [n·c/nit, n·(c+1)/nit) of its long list: the plan bounds each item's
+    //      share with its layers' records, s2c_plan.cpp plan_items), one list entry per
     //      lane and round: k_reads' run records through the tile's long list of run slots, or
     //      for a dense tile (run here in counts-only modes) its long pieces themselves, walked
     //      from HBM (walk_piece) — each run's part in the lane's word W
@@ -1649,7 +1651,13 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(NWP <= 16 ? 
             }
         };
         const bool lpieces = (T.flags & S2C_TILE_DENSE) != 0;
-        const uint32_t nlong = l0 == 0 ? T.lp1 - T.lp0 : 0u;
+        const uint32_t nit = uni(d.tiles[(size_t)tile * S2C_TILE_WORDS + 21]), nlg = T.lp1 - T.lp0;
+        uint32_t e0 = 0, e1 = chunk == 0 ? nlg : 0u;   // (nit 0, a hand-built tile record: the first item takes the list)
+        if (nit > 1) {
+            e0 = (uint32_t)((uint64_t)nlg * min(chunk, nit) / nit);
+            e1 = (uint32_t)((uint64_t)nlg * min(chunk + 1, nit) / nit);
+        }
+        const uint32_t nlong = e1 - e0;
         const uint32_t ntr = uni(__ockl_wfred_max_u32(active && g < nlong ? (nlong - g + G - 1) / G : 0u));
         for (uint32_t m = 0; m < ntr; m++) {
             // (a walked piece adds at most one to a position: its runs cover disjoint positions)
@@ -1657,7 +1665,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(NWP <= 16 ? 
             acc++;
             const uint32_t j = g + G * m;
             if (!(active && j < nlong)) continue;
-            const uint32_t e = d.lp[T.lp0 + j];
+            const uint32_t e = d.lp[T.lp0 + e0 + j];
             if (lpieces) {
                 const uint4 P = ((const uint4 *)d.pc)[e];
                 walk_piece(TileMem{d.ops, d.bq, d.bx}, P, d.pc[4 * (size_t)e + 6], d.maxdel_active != 0, d.maxdel,

@@ -77,15 +77,15 @@ def model_reads(hb, maxdel_active=None, maxdel=None, with_piece=False):
         toks = [(int(w) & 15, int(w) >> 4) for w in ops[o:oend]]
         drop = False
         if maxdel_active:   # :210 — '-' of seqout: D/N/P lengths + '-' chars of the bases taken
-            dashes, start = 0, 0
+            dashes, start = sum(ln for op, ln in toks if op in OP_DASH), 0
             for op, ln in toks:
+                if dashes > maxdel:   # (decided: the '-' chars of SEQ can only add)
+                    break
                 if op in OP_BASES:
                     take = max(0, min(ln, slen - start))
                     if take and fl & PF_X:   # '-' chars of SEQ: only reads with non-ACGT chars
                         dashes += int((plane_codes(hb, q0 + start, take) == 5).sum())
                     start += ln
-                elif op in OP_DASH:
-                    dashes += ln
                 elif op in (OP_I, OP_S):
                     start += ln
             drop = dashes > maxdel
@@ -298,7 +298,8 @@ def check_layers(hb):
     arrays' own 16-byte phases; every other tile's layers are exact copies, in start-word
     order, of the short pieces of its proportional per-start-word slices (records, op words,
     the planes of SEQ[0:len]), 16-byte aligned, within the chunk's caps; records per word
-    and counting lane; every item's records per word fit its u16 histogram."""
+    and counting lane; every item's records per word, its long runs included, fit its u16
+    histogram (check_items)."""
     hb.ensure_layers(dense=True)
     i = hb.info
     pc = hb.pc.astype(np.int64)
@@ -350,14 +351,47 @@ def check_layers(hb):
                 for W in range(W0, W1):
                     a = max(W - K, S0) - S0
                     assert recs[a:W - S0 + 1].sum() <= CHUNK_LANE_RECS * G
-        items = [it for it in hb.items.astype(np.int64) if it[0] == t]
-        for _, _, l0, l1 in items:
-            lo0, _ = lays[l0]
-            _, hi1 = lays[l1 - 1]
-            rec = pc[hi1, 2] - pc[lo0, 2]
+    check_items(hb)
+
+
+def check_items(hb):
+    """Every work item's u16 histogram halves stay <= ITEM_RECS: per word W of its tile, the run
+    records of its layers' short pieces starting in words W - kwin .. W, plus its share of the
+    tile's long list (item c of nit, tile word 21, counts entries [n·c/nit, n·(c+1)/nit)) — at
+    most its entries, and at most the long pieces over W (a piece's runs cover a position
+    once).  Returns the largest such sum."""
+    i = hb.info
+    pc = hb.pc.astype(np.int64)
+    NP, K = i.n_pieces, i.kwin
+    T = hb.tiles.astype(np.int64)
+    lng = ((pc[:NP, 3] >> 24) & PF_LONG) != 0
+    sops = np.concatenate([[0], np.cumsum(np.where(lng, 0, pc[1:NP + 1, 2] - pc[:NP, 2]))])   # short pieces' op slots
+    lw = np.zeros(i.n_words + 1, dtype=np.int64)
+    for k in np.nonzero(lng)[0]:
+        span = _span(hb, int(k))
+        if span:
+            lw[pc[k, 0] >> 5] += 1
+            lw[((pc[k, 0] + span - 1) >> 5) + 1] -= 1
+    lw = np.cumsum(lw)
+    by_tile = {}
+    for t, c, l0, l1 in hb.items.astype(np.int64):
+        by_tile.setdefault(int(t), []).append((int(c), int(l0), int(l1)))
+    most = 0
+    for t, its in by_tile.items():
+        nit, nlg = len(its), int(T[t, 11] - T[t, 10])
+        assert T[t, 21] == nit and sorted(c for c, _, _ in its) == list(range(nit))
+        S0, W0, W1, lays = layer_ranges(hb, t)
+        for c, l0, l1 in its:
+            share = nlg * (c + 1) // nit - nlg * c // nit
+            rec = np.zeros(W1 - S0, dtype=np.int64)
+            if l1 > l0:
+                rec = sops[lays[l1 - 1][1]] - sops[lays[l0][0]]
             for W in range(W0, W1):
                 a = max(W - K, S0) - S0
-                assert rec[a:W - S0 + 1].sum() <= ITEM_RECS
+                r = int(rec[a:W - S0 + 1].sum()) + min(share, int(lw[W]))
+                assert r <= ITEM_RECS, (t, c, W, r)
+                most = max(most, r)
+    return most
 
 
 def _codes(bq, bx, q, n):
@@ -433,10 +467,11 @@ def model_columns(events):
     return cols
 
 
-def model_pipeline(hb, thresholds, min_depth=1, fill=b"-", maxdel_active=None, counts_add=None):
+def model_pipeline(hb, thresholds, min_depth=1, fill=b"-", maxdel_active=None, counts_add=None, reads=None):
     """(stats[R,T,4], offs[T*nb+1], out bytes) as the device produces them; ``counts_add``:
-    running totals of earlier streamed batches added to this batch's counts."""
-    runs, events = model_reads(hb, maxdel_active)
+    running totals of earlier streamed batches added to this batch's counts; ``reads``: the
+    batch's model_reads result, where the caller has it."""
+    runs, events = model_reads(hb, maxdel_active) if reads is None else reads
     counts = model_counts(hb, runs)
     if counts_add is not None:
         counts = counts + counts_add
