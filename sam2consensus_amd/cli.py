@@ -12,6 +12,8 @@ import os
 import sys
 import time
 
+from . import table
+
 __version__ = "2.1"
 DESCRIPTION = """
 +------------------------------------------------------------------+
@@ -157,6 +159,14 @@ def insertions_of(parser, args):
     return n
 
 
+def tables_of(parser, args):
+    """The tables the flags ask for as ``table.request``'s mapping: ``counts``, ``depth`` and
+    ``lowcov`` without parameters, the others with what ``variants_of``, ``insertions_of`` and
+    ``links_of`` return (their checks, in that order)."""
+    return table.request(counts=args.counts, variants=variants_of(parser, args), depth=args.depth, lowcov=args.lowcov,
+                         insertions=insertions_of(parser, args), links=links_of(parser, args))
+
+
 class RunResult:
     def __init__(self, files, timings, info, pending=None):
         self.files = files          # {filename: bytes}
@@ -172,30 +182,30 @@ class RunResult:
         return self
 
 
-def consensus_batch(hb, thresholds, prefix, min_depth=1, fill=b"-", nchar=0, device=None, timings=None,
-                    counts=False, variants=None, depth=False, lowcov=False, insertions=None, links=None):
-    """Device pipeline on a parsed HostBatch → {``REF__PREFIX.fasta``: bytes}; with ``counts``
-    also the ``REF__PREFIX.counts.tsv`` count tables (table.py), after the FASTA entries, and
-    with ``variants`` = (min_alt, min_frac) the ``REF__PREFIX.variants.tsv`` tables of mixed
-    sites (coverage at least max(min_depth, 1)) after those, with ``depth`` the
-    ``REF__PREFIX.depth.tsv`` intervals of equal coverage, with ``lowcov`` the
-    ``REF__PREFIX.lowcov.tsv`` runs of coverage below max(min_depth, 1), and last, with
-    ``depth``, the one ``PREFIX.depth_summary.tsv``; with ``insertions`` = min_reads the
-    ``REF__PREFIX.insertions.tsv`` insertion motif tables after all of those, and with ``links`` =
-    (min_alt, min_frac, min_reads) the ``REF__PREFIX.links.tsv`` link tables last — the run then
-    takes the counts route (``Workspace.run_with_tables``)."""
+# the tables whose engine rule begins with the least coverage max(-m, 1) (Workspace.run_with_tables)
+LEAST_FIRST = ("variants", "depth", "lowcov", "links")
+
+
+def consensus_batch(hb, thresholds, prefix, min_depth=1, fill=b"-", nchar=0, device=None, timings=None, **tables):
+    """Device pipeline on a parsed HostBatch → {``REF__PREFIX.fasta``: bytes}.  ``tables``: the
+    text tables to add, by the keys of ``table.TABLES`` (``table.request`` normalises them) —
+    ``counts``, ``depth``, ``lowcov`` = True, ``variants`` = (min_alt, min_frac), ``insertions`` =
+    min_reads, ``links`` = (min_alt, min_frac, min_reads); the sites of ``variants`` and ``links``,
+    ``depth``'s ``passed`` and ``lowcov``'s cut take the least coverage max(min_depth, 1).  Their
+    ``REF__PREFIX<suffix>`` files follow the FASTA entries table by table in ``TABLES`` order, the
+    one ``PREFIX.depth_summary.tsv`` of ``depth`` where ``table.SUMMARY_AFTER`` puts it — the run
+    then takes the counts route (``Workspace.run_with_tables``)."""
     import torch
 
     from .engine import _UPLOADERS, DeviceBatch, Workspace, needs_dense_layers, to_host
-    from .records import build_records, render
+    from .records import fasta_files
 
     t = timings if timings is not None else {}
     t0 = time.perf_counter()
-    runs = bool(depth) or bool(lowcov)
-    tables = bool(counts) or variants is not None or runs or insertions is not None or links is not None
-    db = DeviceBatch(hb, device, dense_layers=needs_dense_layers(fill, tables))
+    req = table.request(**tables)
+    db = DeviceBatch(hb, device, dense_layers=needs_dense_layers(fill, bool(req)))
     t1 = time.perf_counter()
-    ws = Workspace(db, thresholds, min_depth, fill, keep_counts=tables)
+    ws = Workspace(db, thresholds, min_depth, fill, keep_counts=bool(req))
     torch.cuda.synchronize(db.device)
     t["h2d"] = time.perf_counter() - t0
     t["h2d_issue"] = t1 - t0   # (layers + pinned staging + copies issued; the rest: workspace + drain)
@@ -203,18 +213,10 @@ def consensus_batch(hb, thresholds, prefix, min_depth=1, fill=b"-", nchar=0, dev
     if up is not None:   # (the pinned ring's cumulative host seconds: alloc, wait, pack, issue)
         t.update(("h2d_up_" + k, v) for k, v in up.timing.items())
     t0 = time.perf_counter()
-    if tables:
-        sites = (max(int(min_depth), 1),) + tuple(variants) if variants is not None else None
-        least = max(int(min_depth), 1)
-        res = ws.run_with_tables(counts=bool(counts), sites=sites, depth=least if depth else None,
-                                 lowcov=least if lowcov else None, insertions=insertions,
-                                 links=(least,) + tuple(links) if links is not None else None)
-        # (counts, sites[, depth, lowcov][, insertions][, links]: run_with_tables' docstring)
-        ktab = res[-1] if links is not None else None
-        res = res[:-1] if links is not None else res
-        itab = res[-1] if insertions is not None else None
-        ctab, stab = res[:2]
-        dtab, ltab = res[2:4] if runs else (None, None)
+    res = {}
+    if req:
+        least = (max(int(min_depth), 1),)
+        res = ws.run_with_tables({k: (least if k in LEAST_FIRST else ()) + v for k, v in req.items()})
     else:
         ws.run()
     torch.cuda.synchronize(db.device)
@@ -223,26 +225,13 @@ def consensus_batch(hb, thresholds, prefix, min_depth=1, fill=b"-", nchar=0, dev
     t["device"] = time.perf_counter() - t0
     t["device_run"] = t1 - t0   # (the launches to completion; the rest: the results' D2H)
     t0 = time.perf_counter()
-    fastas = build_records(hb, thresholds, prefix, stats, offs, out)
-    pre = prefix.encode("latin-1") if isinstance(prefix, str) else prefix
-    files = {}
-    for name, recs in fastas.items():
-        files[name.encode("latin-1") + b"__" + pre + b".fasta"] = render(recs, nchar)
-    if tables:   # (after build_records: a vote error raises and no file is returned)
-        from . import table as tb
-
-        def text(tab, header, suffix):
-            return lambda: tb.table_files(hb, pre, tab[0], to_host(tab[1]), header, suffix)
-        # (the summary: the host sums the tiles' statistics; it never reads the counts)
-        for asked, make in ((counts, text(ctab, tb.HEADER, tb.SUFFIX)),
-                            (variants is not None, text(stab, tb.SITES_HEADER, tb.SITES_SUFFIX)),
-                            (depth, text(dtab, tb.DEPTH_HEADER, tb.DEPTH_SUFFIX)),
-                            (lowcov, text(ltab, tb.LOWCOV_HEADER, tb.LOWCOV_SUFFIX)),
-                            (depth, lambda: tb.summary_file(hb, pre, dtab[2])),
-                            (insertions is not None, text(itab, tb.INS_HEADER, tb.INS_SUFFIX)),
-                            (links is not None, text(ktab, tb.LINKS_HEADER, tb.LINKS_SUFFIX))):
-            if asked:
-                files.update(make())
+    files = fasta_files(hb, thresholds, prefix, nchar, stats, offs, out)
+    for tab in table.TABLES:   # (after the records: a vote error raises and no file is returned)
+        if tab.key in res:
+            files.update(table.table_files(hb, prefix, res[tab.key][0], to_host(res[tab.key][1]), tab.header, tab.suffix))
+        if tab.key == table.SUMMARY_AFTER and "depth" in res:
+            # (the summary: the host sums the tiles' statistics; it never reads the counts)
+            files.update(table.summary_file(hb, prefix, res["depth"][2]))
     t["format"] = time.perf_counter() - t0
     return files
 
@@ -336,25 +325,21 @@ def upload_estimate(filename):
 
 def consensus_batch_hip(sess, hb, thresholds, prefix, min_depth=1, fill=b"-", nchar=0, timings=None):
     """consensus_batch through hiprun.Session (no PyTorch): the one-process CLI's device side."""
-    from .records import build_records, render
+    from .records import fasta_files
 
     t = timings if timings is not None else {}
     t0 = time.perf_counter()
     stats, offs, out = sess.run(hb, thresholds, min_depth, fill, t)
     t["device"] = time.perf_counter() - t0
     t0 = time.perf_counter()
-    fastas = build_records(hb, thresholds, prefix, stats, offs, out)
-    pre = prefix.encode("latin-1") if isinstance(prefix, str) else prefix
-    files = {}
-    for name, recs in fastas.items():
-        files[name.encode("latin-1") + b"__" + pre + b".fasta"] = render(recs, nchar)
+    files = fasta_files(hb, thresholds, prefix, nchar, stats, offs, out)
     t["format"] = time.perf_counter() - t0
     return files
 
 
-def _consensus_files_tables(filename, thresholds, prefix, min_depth, fill, nchar, maxdel_active, device, log,
-                            counts, variants, depth=False, lowcov=False, insertions=None, links=None):
-    """consensus_files with any of the tables: the torch engine path (consensus_batch)."""
+def _consensus_files_tables(filename, thresholds, prefix, min_depth, fill, nchar, maxdel_active, device, log, req):
+    """consensus_files with the tables of ``req`` (table.request): the torch engine path
+    (consensus_batch)."""
     import torch
 
     from . import _lib
@@ -379,26 +364,20 @@ def _consensus_files_tables(filename, thresholds, prefix, min_depth, fill, nchar
     t["parse"] = time.perf_counter() - t0
     if log:
         _log_summary(log, hb.info)
-    files = consensus_batch(hb, thresholds, prefix, min_depth, fill, nchar, dev, t, counts=counts, variants=variants,
-                            depth=depth, lowcov=lowcov, insertions=insertions, links=links)
+    files = consensus_batch(hb, thresholds, prefix, min_depth, fill, nchar, dev, t, **req)
     return RunResult(files, t, hb.info, hb.free_async())
 
 
 def consensus_files(filename, thresholds, prefix, min_depth=1, fill=b"-", nchar=0, maxdel_active=True,
-                    device=None, log=None, counts=False, variants=None, depth=False, lowcov=False, insertions=None,
-                    links=None):
+                    device=None, log=None, **tables):
     """Run the whole pipeline on one SAM/SAM.gz file; returns a RunResult whose
     ``files`` maps ``REF__PREFIX.fasta`` → content bytes (nothing written).  The device side
     runs through the HIP runtime directly (hiprun.py): this path never imports PyTorch.
-    With ``counts`` the files also hold the ``REF__PREFIX.counts.tsv`` count tables, with
-    ``variants`` = (min_alt, min_frac) the ``REF__PREFIX.variants.tsv`` tables of mixed sites,
-    with ``depth`` / ``lowcov`` the ``.depth.tsv`` / ``.lowcov.tsv`` runs of coverage (and the
-    depth summary), with ``insertions`` = min_reads the ``.insertions.tsv`` insertion motif tables,
-    with ``links`` = (min_alt, min_frac, min_reads) the ``.links.tsv`` link tables, and the run goes
-    through the torch engine path instead (``consensus_batch``)."""
-    if counts or variants is not None or depth or lowcov or insertions is not None or links is not None:
-        return _consensus_files_tables(filename, thresholds, prefix, min_depth, fill, nchar, maxdel_active, device, log,
-                                       bool(counts), variants, bool(depth), bool(lowcov), insertions, links)
+    With any of ``consensus_batch``'s ``tables`` the files also hold those tables, and the run
+    goes through the torch engine path instead (``consensus_batch``)."""
+    req = table.request(**tables)
+    if req:
+        return _consensus_files_tables(filename, thresholds, prefix, min_depth, fill, nchar, maxdel_active, device, log, req)
     from .batch import Parser
     from .hiprun import Session, device_index
 
@@ -430,31 +409,22 @@ def consensus_files(filename, thresholds, prefix, min_depth=1, fill=b"-", nchar=
     return RunResult(files, t, hb.info, hb.free_async())
 
 
-def run_text(sam_text, argv, device=None, counts=False, variants=None, depth=False, lowcov=False, insertions=None,
-             links=None):
+def run_text(sam_text, argv, device=None, **tables):
     """Library entry for tests: SAM text + CLI args (without -i) → (status, {fname: str}).
     status is "ok" or the reference's exception class name; nothing touches the disk.
-    ``counts`` (or ``--counts`` among the args): the count tables too; ``variants`` =
-    (min_alt, min_frac) (or ``--variants`` and its options among the args): the tables of
-    mixed sites too; ``depth`` / ``lowcov`` (or ``--depth`` / ``--lowcov``): the depth intervals
-    with their summary / the low-coverage runs too; ``insertions`` = min_reads (or ``--insertions``
-    and ``--min-ins-reads``): the insertion motif tables too; ``links`` = (min_alt, min_frac,
-    min_reads) (or ``--links`` and its options): the link tables too."""
+    ``tables``: ``consensus_batch``'s; a table given among the args (``--variants`` and its
+    options, ...) is added, and wins over its keyword."""
     from .batch import parse_text
 
     parser = build_parser()
     args = parser.parse_args(["-i", "in.sam"] + list(argv))
-    variants = variants_of(parser, args) or variants
-    insertions = insertions_of(parser, args) or insertions
-    links = links_of(parser, args) or links
+    req = {**table.request(**tables), **tables_of(parser, args)}
     try:
         thresholds = [float(i) for i in args.thresholds.split(",")]
         prefix = args.prefix or "in"
         hb = parse_text(sam_text, not isinstance(args.maxdel, str), 150)
         files = consensus_batch(hb, thresholds, os.fsencode(prefix), args.min_depth,
-                                os.fsencode(args.fill), args.n, device, counts=bool(counts or args.counts),
-                                variants=variants, depth=bool(depth or args.depth), lowcov=bool(lowcov or args.lowcov),
-                                insertions=insertions, links=links)
+                                os.fsencode(args.fill), args.n, device, **req)
     except (KeyError, IndexError, ValueError, ZeroDivisionError, OverflowError) as e:
         return type(e).__name__, {}
     return "ok", {k.decode("latin-1"): v.decode("latin-1") for k, v in files.items()}
@@ -484,7 +454,7 @@ def consensus_files_sharded(filename, thresholds, prefix, min_depth, fill, nchar
 
     from .dparse import parse_distributed
     from .engine import DeviceBatch, Workspace, needs_dense_layers
-    from .records import build_records, render
+    from .records import fasta_files
     from .shard import gather_device
 
     world, rank, local = _dist_env()
@@ -515,24 +485,18 @@ def consensus_files_sharded(filename, thresholds, prefix, min_depth, fill, nchar
     if rank != 0:
         return None
     P.hb.ref_reads = P.ref_flags   # Σcoverage > 0 over every rank's reads (:334-341)
-    fastas = build_records(P.hb, thresholds, prefix, *res)
-    pre = prefix.encode("latin-1") if isinstance(prefix, str) else prefix
-    return {n.encode("latin-1") + b"__" + pre + b".fasta": render(r, nchar) for n, r in fastas.items()}
+    return fasta_files(P.hb, thresholds, prefix, nchar, *res)
 
 
 def main(argv=None):
     parser = build_parser()
     args = parser.parse_args(argv)
-    variants = variants_of(parser, args)
-    insertions = insertions_of(parser, args)
-    links = links_of(parser, args)
-    for flag, on in (("--counts", args.counts), ("--variants", variants is not None), ("--depth", args.depth),
-                     ("--lowcov", args.lowcov), ("--insertions", insertions is not None), ("--links", links is not None)):
-        if on:   # (refused before a folder is made or a device touched)
-            if _dist_env()[0] > 1:
-                parser.error(flag + " is not available with more than one process (WORLD_SIZE > 1)")
-            if os.environ.get("S2C_STREAM"):
-                parser.error(flag + " is not available with streamed batches (S2C_STREAM)")
+    req = tables_of(parser, args)
+    for key in req:   # (refused before a folder is made or a device touched)
+        if _dist_env()[0] > 1:
+            parser.error("--" + key + " is not available with more than one process (WORLD_SIZE > 1)")
+        if os.environ.get("S2C_STREAM"):
+            parser.error("--" + key + " is not available with streamed batches (S2C_STREAM)")
     filename = args.filename
     thresholds = [float(i) for i in args.thresholds.split(",")]                # :117-118
     if args.prefix == "":
@@ -562,9 +526,7 @@ def main(argv=None):
                                              batch_bytes=sb).files
         else:
             res = consensus_files(filename, thresholds, os.fsencode(prefix), args.min_depth,
-                                  os.fsencode(args.fill), args.n, maxdel_active, log=lambda s: print(s),
-                                  counts=args.counts, variants=variants, depth=args.depth, lowcov=args.lowcov,
-                                  insertions=insertions, links=links)
+                                  os.fsencode(args.fill), args.n, maxdel_active, log=lambda s: print(s), **req)
             files = res.files
     tables = []
     for fname, body in files.items():                                             # :411-424
@@ -572,20 +534,11 @@ def main(argv=None):
         with open(path, "wb") as fh:
             fh.write(body)
         shown = os.fsdecode(path)
-        if args.depth and fname.endswith(b".depth_summary.tsv"):   # (PREFIX alone: no reference)
+        noun = next((t.noun for t in table.TABLES if t.key in req and fname.endswith(t.suffix)), None)
+        if "depth" in req and fname.endswith(table.SUMMARY_SUFFIX):   # (PREFIX alone: no reference)
             tables.append("Depth summary saved in: " + shown)
-        elif args.depth and fname.endswith(b".depth.tsv"):         # (the run tables come after the others, in this order)
-            tables.append("Depth table saved for " + os.fsdecode(fname[: fname.rfind(b"__")]) + " in: " + shown)
-        elif insertions is not None and fname.endswith(b".insertions.tsv"):   # (last: after the depth summary)
-            tables.append("Insertion table saved for " + os.fsdecode(fname[: fname.rfind(b"__")]) + " in: " + shown)
-        elif links is not None and fname.endswith(b".links.tsv"):   # (last of all: after the insertion tables)
-            tables.append("Link table saved for " + os.fsdecode(fname[: fname.rfind(b"__")]) + " in: " + shown)
-        elif args.lowcov and fname.endswith(b".lowcov.tsv"):
-            tables.append("Low-coverage table saved for " + os.fsdecode(fname[: fname.rfind(b"__")]) + " in: " + shown)
-        elif args.counts and fname.endswith(b".counts.tsv"):
-            tables.append("Count table saved for " + os.fsdecode(fname[: fname.rfind(b"__")]) + " in: " + shown)
-        elif variants is not None and fname.endswith(b".variants.tsv"):   # (the files come after the count tables)
-            tables.append("Variant table saved for " + os.fsdecode(fname[: fname.rfind(b"__")]) + " in: " + shown)
+        elif noun is not None:   # (the tables' lines after the consensus lines, in the files' order)
+            tables.append(noun + " saved for " + os.fsdecode(fname[: fname.rfind(b"__")]) + " in: " + shown)
         elif len(thresholds) == 1:
             print("Consensus sequence at " + str(int(thresholds[0] * 100)) + "% saved for " +
                   os.fsdecode(fname[: fname.rfind(b"__")]) + " in: " + shown)

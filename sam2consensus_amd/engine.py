@@ -16,6 +16,7 @@ import torch
 from . import _lib as L
 from ._lib import lib
 from .devargs import EXT_ARRAYS, UPLOAD, fill_dev, fill_ext
+from .table import TABLES
 
 
 def _dev(device):
@@ -564,49 +565,44 @@ class Workspace:
                                       blocks, _ptr(buf["scratch"]), offs, text, total, st))
         return self._two_pass("insertions_table", len_call, write_call, own_checks, filled_by="accumulate")
 
-    def run_with_tables(self, counts=True, sites=None, *, depth=None, lowcov=None, insertions=None, links=None):
-        """``run()`` through the counts route, with any of the tables: every tile's counts
-        stored (s2c_accumulate on zeroed counts, the insertion tables kept), formatted as text
-        (before the vote, which leaves the counts zero), then every tile voted from them
-        (``vote_all``); ``fetch()`` yields the FASTA results as after ``run()``.  ``counts``:
-        the count tables; ``sites`` (min_cov, min_alt, min_frac): the tables of mixed sites.
-        Returns (counts_table() or None, sites_table(*sites) or None): a table not asked for
-        is not formatted.  With ``depth`` = min_cov (the depth intervals, ``passed`` counted at
-        min_cov) or ``lowcov`` = cut (the runs of coverage < cut), two more:
-        (..., depth_table(0, depth) or None, depth_table(lowcov) or None).  With ``insertions`` =
-        min_reads one more element, last: insertions_table(insertions) — formatted before the
-        vote consumes the insertion tables.  With ``links`` = (min_cov, min_alt, min_frac,
-        min_reads) one more, after that: links_table(*links); a rule that ``sites`` has too is
-        marked once."""
+    def run_with_tables(self, request):
+        """``run()`` through the counts route, with the tables of ``request`` (``table.request``'s
+        mapping, a table's parameters those of its method): ``counts: ()``, ``variants: (min_cov,
+        min_alt, min_frac)``, ``depth: (min_cov,)`` (``passed`` counted at min_cov), ``lowcov:
+        (cut,)`` (the runs of coverage < cut), ``insertions: (min_reads,)``, ``links: (min_cov,
+        min_alt, min_frac, min_reads)``.  Every tile's counts are stored (s2c_accumulate on zeroed
+        counts, the insertion tables kept), formatted as text in ``TABLES`` order (before the vote,
+        which leaves the counts zero and consumes the insertion tables), then every tile is voted
+        from them (``vote_all``); ``fetch()`` yields the FASTA results as after ``run()``.  Returns
+        {key: what the table's method returns} for exactly the keys of ``request``; a site rule
+        that ``variants`` and ``links`` share is marked once."""
         if not self.keep_counts:
             raise ValueError("run_with_tables needs Workspace(keep_counts=True)")
-        if lowcov is not None and int(lowcov) < 1:
+        unknown = sorted(set(request) - {t.key for t in TABLES})
+        if unknown:
+            raise TypeError("no such table: " + ", ".join(unknown))
+        if "lowcov" in request and int(request["lowcov"][0]) < 1:
             raise ValueError("run_with_tables: lowcov is the least coverage that passes, >= 1")
+        make = {"counts": self.counts_table, "variants": self.sites_table, "depth": lambda min_cov: self.depth_table(0, min_cov),
+                "lowcov": self.depth_table, "insertions": self.insertions_table, "links": self.links_table}
         self._counts_ready()
         # (set first: if a stage raises, a reused workspace zeroes its counts before its next run)
         self._counts_filled = True
         self.accumulate(keep_tables=True)
         self._site_masks = {}
         try:
-            table = self.counts_table() if counts else None
-            stable = self.sites_table(*sites) if sites is not None else None
-            dtable = self.depth_table(0, depth) if depth is not None else None
-            ltable = self.depth_table(lowcov) if lowcov is not None else None
-            itable = self.insertions_table(insertions) if insertions is not None else None
-            ktable = self.links_table(*links) if links is not None else None
+            res = {t.key: make[t.key](*request[t.key]) for t in TABLES if t.key in request}
         finally:
             self._site_masks = None
         self.vote_all()
-        res = (table, stable) if depth is None and lowcov is None else (table, stable, dtable, ltable)
-        res = res if insertions is None else res + (itable,)
-        return res if links is None else res + (ktable,)
+        return res
 
     def run_with_counts(self):
         """``run_with_tables`` with the count tables alone.  Returns counts_table()'s (offs,
         device text)."""
         if not self.keep_counts:
             raise ValueError("run_with_counts needs Workspace(keep_counts=True)")
-        return self.run_with_tables(counts=True)[0]
+        return self.run_with_tables({"counts": ()})["counts"]
 
     def pileup_counts(self):
         """Diagnostic: k_reads, then every tile's counts stored to `counts` (no vote); needs

@@ -62,3 +62,11 @@ def render(recs, nchar):
         return b"\n".join(h + b"\n" + s for h, s in recs) + b"\n"
     return b"\n".join(h + b"\n" + b"\n".join(s[k:k + nchar] for k in range(0, len(s), nchar))
                       for h, s in recs) + b"\n"
+
+
+def fasta_files(hb, thresholds, prefix, nchar, stats, offs, out):
+    """{``REF__PREFIX.fasta``: bytes} of ``build_records``' records (its errors raise before any
+    file is formed), in reference order."""
+    pre = prefix.encode("latin-1") if isinstance(prefix, str) else prefix
+    return {name.encode("latin-1") + b"__" + pre + b".fasta": render(recs, nchar)
+            for name, recs in build_records(hb, thresholds, prefix, stats, offs, out).items()}

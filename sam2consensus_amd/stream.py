@@ -688,7 +688,7 @@ def consensus_files_streamed(filename, thresholds, prefix, min_depth=1, fill=b"-
                              device=None, log=None, batch_bytes=DEFAULT_BATCH, tile_width=DEFAULT_TILE):
     """``cli.consensus_files`` in streamed batches (unsorted input: counts accumulated)."""
     from .cli import RunResult, _log_summary
-    from .records import build_records, render
+    from .records import fasta_files
 
     t = {}
     t0 = time.perf_counter()
@@ -710,9 +710,7 @@ def consensus_files_streamed(filename, thresholds, prefix, min_depth=1, fill=b"-
     if log:
         _log_summary(log, res)
     t0 = time.perf_counter()
-    fastas = build_records(res.hb, thresholds, prefix, res.stats, res.offs, res.out)
-    pre = prefix.encode("latin-1") if isinstance(prefix, str) else prefix
-    files = {n.encode("latin-1") + b"__" + pre + b".fasta": render(r, nchar) for n, r in fastas.items()}
+    files = fasta_files(res.hb, thresholds, prefix, nchar, res.stats, res.offs, res.out)
     t["format"] = time.perf_counter() - t0
     r = RunResult(files, t, res.hb.info)
     r.batches = res.batches

@@ -56,6 +56,8 @@ count falling, then by ``(s1, s2)`` in ``-ACGNT`` order — a total order.  A pa
 """
 from __future__ import annotations
 
+import collections
+
 import numpy as np
 
 HEADER = b"pos\tcov\t-\tA\tC\tG\tN\tT\n"
@@ -74,6 +76,31 @@ INS_HEADER = b"pos\tcov\treads\tlen\tmotif\n"
 INS_SUFFIX = b".insertions.tsv"
 LINKS_HEADER = b"pos1\tpos2\treads\thaps\tpairs\n"
 LINKS_SUFFIX = b".links.tsv"
+
+# Every per-reference table, in file order and launch order; the command-line flag is "--" + key,
+# the stdout line "<noun> saved for REF in: PATH".  The one file that is no per-reference table,
+# the depth summary (with ``depth``), comes after the tables of SUMMARY_AFTER.
+Table = collections.namedtuple("Table", "key suffix header noun")
+TABLES = (Table("counts", SUFFIX, HEADER, "Count table"),
+          Table("variants", SITES_SUFFIX, SITES_HEADER, "Variant table"),
+          Table("depth", DEPTH_SUFFIX, DEPTH_HEADER, "Depth table"),
+          Table("lowcov", LOWCOV_SUFFIX, LOWCOV_HEADER, "Low-coverage table"),
+          Table("insertions", INS_SUFFIX, INS_HEADER, "Insertion table"),
+          Table("links", LINKS_SUFFIX, LINKS_HEADER, "Link table"))
+SUMMARY_AFTER = "lowcov"
+
+
+def request(**kw):
+    """The tables asked for by keyword as one mapping {key: parameter tuple} in ``TABLES`` order:
+    ``True`` gives ``()``, ``False`` / ``None`` leaves the table out, a bare number (``insertions``'
+    min_reads) gives a 1-tuple, a sequence its tuple.  A keyword that names no table is a
+    ``TypeError``."""
+    unknown = sorted(set(kw) - {t.key for t in TABLES})
+    if unknown:
+        raise TypeError("no such table: " + ", ".join(unknown))
+    asked = ((t.key, kw.get(t.key)) for t in TABLES)
+    return {k: () if v is True else tuple(v) if isinstance(v, (tuple, list)) else (v,)
+            for k, v in asked if v is not None and v is not False}
 
 
 def format_rows(counts_6xL, p0=1):

@@ -96,8 +96,8 @@ def main():
     r_counts, r_depth, r_low = [], [], []
     for _ in range(a.reps):
         r_counts += wall(ws.run_with_counts, 1)
-        r_depth += wall(lambda: ws.run_with_tables(counts=False, depth=least), 1)
-        r_low += wall(lambda: ws.run_with_tables(counts=False, lowcov=least), 1)
+        r_depth += wall(lambda: ws.run_with_tables({"depth": (least,)}), 1)
+        r_low += wall(lambda: ws.run_with_tables({"lowcov": (least,)}), 1)
     sites_ms = min(s_mark) + min(s_len) + min(s_write)
     table_ms = min(t_len) + min(t_write)
     res.update({"positions": positions, "sites": n_sites, "sites_bytes": s_total, "table_bytes": t_total,

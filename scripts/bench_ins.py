@@ -68,7 +68,7 @@ def one(tag, over, a, dev):
     r_counts, r_ins = [], []
     for _ in range(a.reps):
         r_counts += wall(ws.run_with_counts, 1)
-        r_ins += wall(lambda: ws.run_with_tables(counts=False, insertions=1), 1)
+        r_ins += wall(lambda: ws.run_with_tables({"insertions": (1,)}), 1)
     ins_ms, table_ms = min(i_len) + min(i_write), min(t_len) + min(t_write)
     return {tag: {"over": over, "tiles": nt, "events": int(i.n_ins), "event_bases": int(i.n_ins_bases), "hash_slots": n_bkt,
                   "long_slots": n_lng, "short_entries": short_entries, "long_events": long_events, "lines": lines, "bytes": total,

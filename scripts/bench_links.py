@@ -97,8 +97,8 @@ def main():
     del pairs
     r_sites, r_links = [], []
     for _ in range(a.reps):
-        r_sites += wall(lambda: ws.run_with_tables(counts=False, sites=prm), 1)
-        r_links += wall(lambda: ws.run_with_tables(counts=False, links=prm + (1,)), 1)
+        r_sites += wall(lambda: ws.run_with_tables({"variants": prm}), 1)
+        r_links += wall(lambda: ws.run_with_tables({"links": prm + (1,)}), 1)
     links_ms = min(t_rank) + min(t_count) + min(l_len) + min(l_write)
     res = {"workload": a.config, "scale": a.scale, "device": torch.cuda.get_device_name(dev),
            "min_cov": prm[0], "min_alt": prm[1], "min_frac": prm[2],

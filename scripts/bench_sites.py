@@ -84,7 +84,7 @@ def main():
     t_counts, t_sites = [], []
     for _ in range(a.reps):
         t_counts += wall(ws.run_with_counts, 1)
-        t_sites += wall(lambda: ws.run_with_tables(counts=False, sites=prm), 1)
+        t_sites += wall(lambda: ws.run_with_tables({"variants": prm}), 1)
     sites_ms = min(t_mark) + min(t_len) + min(t_write)
     table_ms = min(t_tlen) + min(t_twrite)
     res = {"workload": "c5", "scale": a.scale, "positions": positions, "tiles": nt,

@@ -605,8 +605,8 @@ def test_all_four_tables_equal_the_separate_runs():
 @pytest.mark.gpu
 def test_workspace_reuse():
     """run_with_tables with the run tables twice on one workspace: the same tables, statistics
-    and FASTA results; for its present arguments it still returns its 2-tuple; depth_table
-    needs filled counts."""
+    and FASTA results; it returns exactly the tables asked for; depth_table needs filled
+    counts."""
     import torch
     from sam2consensus_amd import configs
     from sam2consensus_amd.engine import DeviceBatch, Workspace
@@ -624,9 +624,9 @@ def test_workspace_reuse():
         ws.depth_table()          # (nothing has filled the counts)
     runs = []
     for _ in range(2):
-        res = ws.run_with_tables(counts=False, depth=2, lowcov=2)
-        assert len(res) == 4 and res[0] is None and res[1] is None and res[3][2] is None
-        (doffs, dtext, dstats), (loffs, ltext, _) = res[2:]
+        res = ws.run_with_tables({"depth": (2,), "lowcov": (2,)})
+        assert list(res) == ["depth", "lowcov"] and res["lowcov"][2] is None
+        (doffs, dtext, dstats), (loffs, ltext, _) = res["depth"], res["lowcov"]
         runs.append((doffs.tobytes(), dtext.cpu().numpy().tobytes(), dstats.tobytes(), loffs.tobytes(),
                      ltext.cpu().numpy().tobytes(), fetched(ws)))
     assert runs[0] == runs[1] and runs[0][5] == base
@@ -636,12 +636,12 @@ def test_workspace_reuse():
     got.update(table.table_files(hb, b"x", loffs, runs[0][4], table.LOWCOV_HEADER, table.LOWCOV_SUFFIX))
     got.update(table.summary_file(hb, b"x", dstats))
     assert got == want
-    two = ws.run_with_tables(counts=True, sites=(1, 2, 0.05))
-    assert len(two) == 2 and fetched(ws) == base
-    one = ws.run_with_tables(counts=False, lowcov=2)
-    assert len(one) == 4 and one[2] is None and one[3][1].cpu().numpy().tobytes() == runs[0][4] and fetched(ws) == base
+    two = ws.run_with_tables({"counts": (), "variants": (1, 2, 0.05)})
+    assert list(two) == ["counts", "variants"] and fetched(ws) == base
+    one = ws.run_with_tables({"lowcov": (2,)})
+    assert set(one) == {"lowcov"} and one["lowcov"][1].cpu().numpy().tobytes() == runs[0][4] and fetched(ws) == base
     with pytest.raises(ValueError):
-        ws.run_with_tables(counts=False, lowcov=0)
+        ws.run_with_tables({"lowcov": (0,)})
     torch.cuda.synchronize()
 
 

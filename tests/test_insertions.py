@@ -701,21 +701,21 @@ def test_workspace_reuse():
         ws.insertions_table()          # (nothing has filled the counts or the tables)
     runs = []
     for _ in range(2):
-        res = ws.run_with_tables(counts=False, insertions=1)
-        assert len(res) == 3 and res[0] is None and res[1] is None
-        offs, text = res[2]
+        res = ws.run_with_tables({"insertions": (1,)})
+        assert set(res) == {"insertions"}
+        offs, text = res["insertions"]
         runs.append((offs.tobytes(), text.cpu().numpy().tobytes(), fetched(ws)))
         with pytest.raises(ValueError):
             ws.insertions_table()      # (vote_all consumed the tables)
     assert runs[0] == runs[1] and runs[0][2] == base
     want, _ = _model_ins(hb, b"x")
     assert table.table_files(hb, b"x", offs, runs[0][1], table.INS_HEADER, table.INS_SUFFIX) == want
-    five = ws.run_with_tables(counts=True, depth=1, insertions=2)
-    assert len(five) == 5 and fetched(ws) == base
-    assert table.table_files(hb, b"x", five[4][0], five[4][1].cpu().numpy().tobytes(), table.INS_HEADER,
+    three = ws.run_with_tables({"counts": (), "depth": (1,), "insertions": (2,)})
+    assert list(three) == ["counts", "depth", "insertions"] and fetched(ws) == base
+    assert table.table_files(hb, b"x", three["insertions"][0], three["insertions"][1].cpu().numpy().tobytes(), table.INS_HEADER,
                              table.INS_SUFFIX) == _model_ins(hb, b"x", 2)[0]
-    two = ws.run_with_tables(counts=True)
-    assert len(two) == 2 and fetched(ws) == base
+    two = ws.run_with_tables({"counts": ()})
+    assert set(two) == {"counts"} and fetched(ws) == base
     ws.accumulate(keep_tables=True)   # (onto the counts the vote left zero)
     with pytest.raises(ValueError):
         ws.insertions_table(0)

@@ -780,26 +780,27 @@ def test_workspace_reuse():
         ws.links_table()
     runs = []
     for _ in range(2):
-        res = ws.run_with_tables(counts=False, links=(1, 8, 0.0, 1))
-        assert len(res) == 3 and res[0] is None and res[1] is None
-        offs, text = res[2]
+        res = ws.run_with_tables({"links": (1, 8, 0.0, 1)})
+        assert set(res) == {"links"}
+        offs, text = res["links"]
         runs.append((offs.tobytes(), text.cpu().numpy().tobytes(), fetched(ws)))
     assert runs[0] == runs[1] and runs[0][2] == base
     want, _ = _model_links(hb, b"x", (8, 0.0))
     assert table.table_files(hb, b"x", offs, runs[0][1], table.LINKS_HEADER, table.LINKS_SUFFIX) == want
-    alone = ws.run_with_tables(counts=False, sites=(1, 8, 0.0))
-    sites_text = alone[1][1].cpu().numpy().tobytes()
-    six = ws.run_with_tables(counts=True, sites=(1, 8, 0.0), depth=1, insertions=1, links=(1, 8, 0.0, 2))
-    assert len(six) == 6 and fetched(ws) == base
-    assert six[1][1].cpu().numpy().tobytes() == sites_text
-    assert table.table_files(hb, b"x", six[5][0], six[5][1].cpu().numpy().tobytes(), table.LINKS_HEADER,
+    alone = ws.run_with_tables({"variants": (1, 8, 0.0)})
+    sites_text = alone["variants"][1].cpu().numpy().tobytes()
+    six = ws.run_with_tables({"links": (1, 8, 0.0, 2), "insertions": (1,), "lowcov": (1,), "depth": (1,), "variants": (1, 8, 0.0),
+                              "counts": ()})   # (the request's own order does not matter)
+    assert list(six) == ["counts", "variants", "depth", "lowcov", "insertions", "links"] and fetched(ws) == base
+    assert six["variants"][1].cpu().numpy().tobytes() == sites_text
+    assert table.table_files(hb, b"x", six["links"][0], six["links"][1].cpu().numpy().tobytes(), table.LINKS_HEADER,
                              table.LINKS_SUFFIX) == _model_links(hb, b"x", (8, 0.0), 2)[0]
-    other = ws.run_with_tables(counts=False, sites=(1, 8, 0.0), links=(1, 12, 0.0, 1))   # (two rules: two masks)
-    assert len(other) == 3 and other[1][1].cpu().numpy().tobytes() == sites_text
-    assert table.table_files(hb, b"x", other[2][0], other[2][1].cpu().numpy().tobytes(), table.LINKS_HEADER,
+    other = ws.run_with_tables({"variants": (1, 8, 0.0), "links": (1, 12, 0.0, 1)})   # (two rules: two masks)
+    assert list(other) == ["variants", "links"] and other["variants"][1].cpu().numpy().tobytes() == sites_text
+    assert table.table_files(hb, b"x", other["links"][0], other["links"][1].cpu().numpy().tobytes(), table.LINKS_HEADER,
                              table.LINKS_SUFFIX) == _model_links(hb, b"x", (12, 0.0))[0]
-    two = ws.run_with_tables(counts=True)
-    assert len(two) == 2 and fetched(ws) == base
+    two = ws.run_with_tables({"counts": ()})
+    assert set(two) == {"counts"} and fetched(ws) == base
     ws.accumulate(keep_tables=True)   # (onto the counts the vote left zero)
     with pytest.raises(ValueError):
         ws.links_table(1, 8, 0.0, 0)
@@ -875,3 +876,55 @@ def test_cli_process(tmp_path):
     assert so[:k - 10] + so[k:] == head
     assert {fn: v for fn, v in files.items() if not fn.endswith(".links.tsv")} == base and len(files) == len(base) + 10
     assert {fn: v.decode() for fn, v in files.items() if fn.endswith(".links.tsv")} == want
+
+
+@pytest.mark.gpu
+def test_cli_process_all_six_flags(tmp_path, capsys):
+    """sam2consensus.py with all six table flags in one process on the C1-sized file of
+    test_cli_process: after the consensus lines and before Done. the stdout lines are the count,
+    variant, depth and low-coverage tables' (ten each, in reference order), the one depth summary
+    line, then the insertion and the link tables'; the folder holds the 10 FASTA files, 60 tables
+    and the summary; every table file is what the run with its flag alone writes."""
+    import subprocess
+    import sys
+    from sam2consensus_amd import configs
+    from sam2consensus_amd.batch import parse_file
+    from sam2consensus_amd.cli import main
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sam = str(tmp_path / "c1.sam")
+    configs.synth_write("c1", sam, depth=30.0, ins_frac=0.2, ins_max=6)
+    hb = parse_file(sam)
+    names = list(hb.names)
+    hb.free()
+    assert len(names) == 10
+    flags = ["--counts", "--variants", "--depth", "--lowcov", "--insertions", "--links"]
+    out = tmp_path / "every"
+    r = subprocess.run([sys.executable, os.path.join(root, "sam2consensus.py"), "-i", sam, "-o", str(out), "-c", "0.25"] +
+                       flags + ["--min-alt-frac", "0"], capture_output=True, text=True, timeout=240, cwd=root)
+    assert r.returncode == 0, r.stderr[-2000:]
+    so = r.stdout.replace(str(out), "OUT").split("\n")
+    groups = [("Count table", "counts.tsv"), ("Variant table", "variants.tsv"), ("Depth table", "depth.tsv"),
+              ("Low-coverage table", "lowcov.tsv"), None, ("Insertion table", "insertions.tsv"), ("Link table", "links.tsv")]
+    want = ["Consensus sequence at 25%% saved for %s in: OUT/%s__c1.fasta" % (n, n) for n in names]
+    for g in groups:
+        want += ["Depth summary saved in: OUT/c1.depth_summary.tsv"] if g is None else \
+            ["%s saved for %s in: OUT/%s__c1.%s" % (g[0], n, n, g[1]) for n in names]
+    first = so.index(want[0])
+    assert so[first:] == want + ["Done.", "", ""]
+    files = {fn: open(os.path.join(out, fn), "rb").read() for fn in os.listdir(out)}
+    assert sorted(files) == sorted(["%s__c1.%s" % (n, g[1]) for g in groups if g for n in names] +
+                                   [n + "__c1.fasta" for n in names] + ["c1.depth_summary.tsv"])
+    assert len(files) == 71
+    seen = set()
+    for flag in flags:
+        alone = tmp_path / flag[2:]
+        rule = ["--min-alt-frac", "0"] if flag in ("--variants", "--links") else []
+        assert main(["-i", sam, "-o", str(alone), "-c", "0.25", flag] + rule) == 0
+        tables = [fn for fn in os.listdir(alone) if not fn.endswith(".fasta")]
+        assert len(tables) == (11 if flag == "--depth" else 10)
+        for fn in tables:
+            assert files[fn] == open(os.path.join(alone, fn), "rb").read(), fn
+        seen.update(tables)
+    capsys.readouterr()
+    assert len(seen) == 61
+    assert sum(v.count(b"\n") - 1 for fn, v in files.items() if fn.endswith(".links.tsv")) > 10

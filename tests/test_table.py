@@ -98,6 +98,33 @@ def test_parser_has_counts_flag():
     from sam2consensus_amd.cli import build_parser
     assert build_parser().parse_args(["-i", "x.sam"]).counts is False
     assert build_parser().parse_args(["-i", "x.sam", "--counts"]).counts is True
+    with pytest.raises(TypeError):
+        table.request(bogus=True)
+
+
+def test_registry_flags_and_refusals(tmp_path, monkeypatch, capsys):
+    """Every entry of table.TABLES: the parser has the flag -- + key; main with more than one
+    process, and with streamed batches, exits 2 naming that flag and leaves the folder empty.
+    table.request: the public keyword forms as one mapping in TABLES order."""
+    from sam2consensus_amd.cli import build_parser, main
+    assert [t.key for t in table.TABLES] == ["counts", "variants", "depth", "lowcov", "insertions", "links"]
+    assert table.request(links=[1, 0.0, 2], insertions=3, depth=True, lowcov=False, variants=None, counts=True) == \
+        {"counts": (), "depth": (), "insertions": (3,), "links": (1, 0.0, 2)}
+    assert list(table.request(links=(1, 0.0, 2), counts=True)) == ["counts", "links"] and table.request() == {}
+    sam = tmp_path / "in.sam"
+    sam.write_text("@SQ\tSN:g1\tLN:10\nr\t0\tg1\t1\t60\t4M\t*\t0\t0\tAATG\t*\n")
+    monkeypatch.chdir(tmp_path)
+    for t in table.TABLES:
+        flag = "--" + t.key
+        assert getattr(build_parser().parse_args(["-i", "x.sam", flag]), t.key) is True
+        for env, word in (("WORLD_SIZE", "2"), ("S2C_STREAM", "1M")):
+            for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "S2C_STREAM"):
+                monkeypatch.delenv(k, raising=False)
+            monkeypatch.setenv(env, word)
+            with pytest.raises(SystemExit) as e:
+                main(["-i", str(sam), flag, "-o", str(tmp_path / "out")])
+            assert e.value.code == 2 and flag + " is not available with" in capsys.readouterr().err
+            assert sorted(os.listdir(tmp_path)) == ["in.sam"]
 
 
 @pytest.mark.parametrize("env", [{"WORLD_SIZE": "2"}, {"S2C_STREAM": "1M"}], ids=["world2", "stream"])

@@ -490,17 +490,19 @@ def test_workspace_reuse():
     with pytest.raises(ValueError):
         ws.sites_table(1, 2, 0.05)          # (nothing has filled the counts)
     with pytest.raises(ValueError):
-        Workspace(DeviceBatch(hb), [0.25]).run_with_tables(counts=False, sites=(1, 2, 0.05))
+        Workspace(DeviceBatch(hb), [0.25]).run_with_tables({"variants": (1, 2, 0.05)})
     runs = []
     for _ in range(2):
-        ctab, stab = ws.run_with_tables(counts=False, sites=(1, 2, 0.05))
-        assert ctab is None
+        res = ws.run_with_tables({"variants": (1, 2, 0.05)})
+        assert set(res) == {"variants"}
+        stab = res["variants"]
         runs.append((stab[0].tobytes(), stab[1].cpu().numpy().tobytes(), fetched(ws)))
     assert runs[0] == runs[1]
     assert runs[0][2] == base
     want = _model_sites(hb, _model_counts(hb), b"x", 1, 2, 0.05)
     assert table.table_files(hb, b"x", stab[0], runs[0][1], table.SITES_HEADER, table.SITES_SUFFIX) == want
-    ctab, stab2 = ws.run_with_tables(counts=True, sites=(1, 2, 0.05))
+    both = ws.run_with_tables({"counts": (), "variants": (1, 2, 0.05)})
+    ctab, stab2 = both["counts"], both["variants"]
     assert (stab2[0].tobytes(), stab2[1].cpu().numpy().tobytes()) == runs[0][:2] and fetched(ws) == base
     offs, text = ws.run_with_counts()
     assert offs.tobytes() == ctab[0].tobytes() and text.cpu().numpy().tobytes() == ctab[1].cpu().numpy().tobytes()
