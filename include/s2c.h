@@ -154,7 +154,7 @@ int s2c_layout(int64_t *out, int n);
 #define S2C_EPI_KEYS    256  /* insertion keys per tile k_tile's epilogue holds in LDS */
 /* insertion columns per tile k_tile's epilogue holds in LDS, by words per tile */
 #define S2C_LDS_COLS(nwp) ((nwp) <= 16 ? 640 : ((nwp) == 32 ? 448 : 192))
-#define S2C_DENSE_LDS 32768  /* bytes of LDS a dense tile's window may take (one wave per tile) */
+#define S2C_DENSE_LDS 32768  /* bytes of LDS a dense tile's window may take (two waves per tile share it) */
 /* LDS bytes of a dense tile's window of ns op slots and nq base plane words: op words and
    planes {p0, p1} (each 16-byte aligned with 16 bytes of slack: the 16-byte LDS-DMA starts
    at the boundary below the source), run records, the walk's queues (64 entries per wave and
@@ -164,6 +164,22 @@ int s2c_layout(int64_t *out, int n);
 /* the dense kernel's dynamic LDS is at least this: after the count its two waves' counter
    exchange (8,320 bytes each) reuses the window's LDS — the host's occupancy plan counts it */
 #define S2C_DENSE_MIN_LDS 16640
+/* The window of the extension's walk (s2c_dense_lean): no op words but those of its rare pieces
+   (nrop words), planes, run records + pad zero records (8·G, G = 128 / words per tile: what a
+   count group reads past the last), the X-run queue of min(2·nrare, ns + 128) entries.  Never
+   above S2C_DENSE_BYTES(ns, nq) less the op words' share (nrop ≤ ns, pad ≤ 64). */
+#define S2C_DENSE_LEAN_PAD(nwp) (1024 / (nwp))
+#define S2C_DENSE_LEAN_BYTES(ns, nq, nrare, nrop, nwp)                                                      \
+    ((((8 * (nq) + 30) & ~15) + ((4 * (nrop) + 30) & ~15) + 8 * ((ns) + S2C_DENSE_LEAN_PAD(nwp)) +      \
+      4 * (2 * (nrare) < (ns) + 128 ? 2 * (nrare) : (ns) + 128) + 15) & ~15)
+/* The count of k_tile_dense: a wave whose longest lane holds n candidate records reads
+   S2C_DENSE_SLOTS(n) record slots per lane (groups of 8, a last group of 4 for 1-4 records
+   left); a lane's counters reach at most c = those slots + its long-piece rounds, and the
+   counters' exchange moves S2C_DENSE_PAIRS(c) pairs of bit planes, 2,080 bytes per wave and
+   pair, its rows 80 bytes per tile word: S2C_DENSE_XCH_BYTES for the tile's two waves. */
+#define S2C_DENSE_SLOTS(n) (8 * ((n) / 8) + ((n) % 8 > 4 ? 8 : (n) % 8 ? 4 : 0))
+#define S2C_DENSE_PAIRS(c) ((c) < 4 ? 1 : (c) < 16 ? 2 : (c) < 64 ? 3 : 4)
+#define S2C_DENSE_XCH_BYTES(pairs, nwp) (2 * (2080 * (pairs) > 80 * (nwp) ? 2080 * (pairs) : 80 * (nwp)))
 #define S2C_DENSE_QW   4096  /* base plane words of a dense tile's window (17-bit query offsets) */
 /* k_tile's LDS chunk (one per wave): one layer of a tile window, contiguous in the layered arrays: its
    piece records, op words, base planes
@@ -427,6 +443,25 @@ typedef struct {
     int64_t n_drun, n_dnev, n_dxs, n_drare, n_dext;   /* records / entries / rows (not words) */
 } s2c_dense_ext;
 int  s2c_batch_dense_ext_get(const s2c_batch *b, s2c_dense_ext *out);
+/* What the extension's walk needs besides (round 9): with it k_tile_dense stages no op words.
+ *   rop    [n_rop]     the op words of every window's rare pieces, in drare's order: window i's
+ *          block is words [row[i][0], + row[i][1]), brought to LDS with the window's other DMAs.
+ *   roff   [n_roff]    per record of drare (n_roff = n_drare) the offset of its op words in its
+ *          window's block.
+ *   row    [n_row][S2C_DLEAN_WORDS]  {rop0, n} per dense item (filter its rows as dwin's).
+ *   lds    the most S2C_DENSE_LEAN_BYTES of any window; count_max the largest count a lane of
+ *          any window can reach (S2C_DENSE_SLOTS of the longest lane's records of a wave, plus
+ *          its long-piece rounds); pairs = S2C_DENSE_PAIRS(count_max): the launch takes
+ *          max(lds, S2C_DENSE_XCH_BYTES(pairs, words per tile)) bytes of dynamic LDS.
+ * The scalars are those of the whole batch (a shard's: its own); they hold for any subset of
+ * its windows. */
+#define S2C_DLEAN_WORDS 2
+typedef struct {
+    const uint32_t *rop, *roff, *row;
+    int64_t n_rop, n_roff, n_row;
+    int64_t lds, count_max, pairs;
+} s2c_dense_lean;
+int  s2c_batch_dense_lean_get(const s2c_batch *b, s2c_dense_lean *out);
 /* The sub-batch of tiles [t0, t1) for one GPU of a multi-GPU run (positions keep their
  * global coordinates; free it with s2c_batch_free). */
 int  s2c_batch_shard(const s2c_batch *b, int64_t t0, int64_t t1, s2c_batch **out);
@@ -554,10 +589,20 @@ int s2c_run(const s2c_dev *d, void *stream);
  * filtered like dwin): k_tile_dense takes each window's run records by LDS-DMA from drun and
  * walks only the pieces of drare, instead of deriving both from dpc — the same results.  ext =
  * NULL is s2c_pileup / s2c_run; with an extension s2c_dev.dpc is not read and may be NULL.
+ * Since round 9 the extension runs through the _lean entries below; these two keep its checks.
  * S2C_ERR_ARG before any launch (after s2c_dev's own checks): a NULL array with a non-zero count,
  * a negative count, drun not 16-byte aligned, or n_dext != s2c_dev.n_dense. */
 int s2c_pileup_ext(const s2c_dev *d, const s2c_dense_ext *ext, void *stream);
 int s2c_run_ext(const s2c_dev *d, const s2c_dense_ext *ext, void *stream);
+/* (round 9) The extension's walk reads its rare pieces' op words from s2c_dense_lean, device
+ * pointers with row filtered like dwin, and sizes its launch by it: s2c_pileup_lean / s2c_run_lean
+ * are the entries that run it.  ext = lean = NULL is s2c_pileup / s2c_run; an extension without
+ * its lean part (the _ext entries with ext != NULL included) is S2C_ERR_ARG, after the checks
+ * above; so are a NULL array with a non-zero count, a negative count, n_roff != n_drare, n_row
+ * != s2c_dev.n_dense, lds outside (0, S2C_DENSE_LDS] or not a 16-byte multiple, pairs outside
+ * [1, 4] or below S2C_DENSE_PAIRS(count_max). */
+int s2c_pileup_lean(const s2c_dev *d, const s2c_dense_ext *ext, const s2c_dense_lean *lean, void *stream);
+int s2c_run_lean(const s2c_dev *d, const s2c_dense_ext *ext, const s2c_dense_lean *lean, void *stream);
 
 /* (ABI 14) FASTA body assembly on the device (:394-418; replaces the host gather of the
  * output's body slots, s2c_gather_bodies): dst[offs[i], offs[i+1]) = out[starts[i], +len)

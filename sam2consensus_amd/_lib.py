@@ -32,6 +32,7 @@ S2C_ITEM_WORDS = 4
 S2C_DWIN_WORDS = 16
 S2C_DPC_WORDS = 3     # compact piece records of the dense windows (ABI 12)
 S2C_DEXT_WORDS = 8    # a dense window's row of the extension (s2c_dense_ext)
+S2C_DLEAN_WORDS = 2   # ... and of its lean part (s2c_dense_lean)
 S2C_CODE_FILL = 0
 S2C_SHORT_MOTIF = 16
 S2C_TILE_DEEP, S2C_TILE_GENERAL, S2C_TILE_DENSE = 1, 2, 4
@@ -80,6 +81,14 @@ class DenseExt(C.Structure):
         [(n, C.c_int64) for n in ("n_drun", "n_dnev", "n_dxs", "n_drare", "n_dext")]
 
 
+class DenseLean(C.Structure):
+    """Mirror of ``s2c_dense_lean`` (include/s2c.h): the rare pieces' op words, their offsets, the
+    windows' rows, and the launch's window bytes, largest lane count and plane pairs; host pointers
+    from ``s2c_batch_dense_lean_get`` or device pointers for ``s2c_run_lean`` / ``s2c_pileup_lean``."""
+    _fields_ = [(n, C.c_void_p) for n in ("rop", "roff", "row")] + \
+        [(n, C.c_int64) for n in ("n_rop", "n_roff", "n_row", "lds", "count_max", "pairs")]
+
+
 class SynthSpec(C.Structure):
     _fields_ = [("n_refs", C.c_int32), ("ref_len", C.c_int64), ("depth", C.c_double),
                 ("read_len", C.c_int32), ("ins_frac", C.c_double), ("ins_max", C.c_int32),
@@ -124,9 +133,9 @@ EXPORTS = [
     "s2c_parser_retain_events", "s2c_parser_detach", "s2c_parser_attach", "s2c_accumulate",
     "s2c_parser_pos_weights", "s2c_parser_checks", "s2c_parser_counters", "s2c_parser_progress", "s2c_gather_bodies", "s2c_copy_bytes", "s2c_parser_pack",
     "s2c_parser_blob_copy", "s2c_parser_unpack",
-    "s2c_batch_layers", "s2c_batch_layers_mode", "s2c_batch_info_get", "s2c_batch_arrays_get", "s2c_batch_dense_ext_get", "s2c_batch_ref_name", "s2c_batch_free", "s2c_batch_shard",
+    "s2c_batch_layers", "s2c_batch_layers_mode", "s2c_batch_info_get", "s2c_batch_arrays_get", "s2c_batch_dense_ext_get", "s2c_batch_dense_lean_get", "s2c_batch_ref_name", "s2c_batch_free", "s2c_batch_shard",
     "s2c_parsecigar", "s2c_synth_feed", "s2c_synth_write",
-    "s2c_workspace_sizes", "s2c_reads", "s2c_pileup", "s2c_consensus", "s2c_run", "s2c_pileup_ext", "s2c_run_ext", "s2c_pileup_counts",
+    "s2c_workspace_sizes", "s2c_reads", "s2c_pileup", "s2c_consensus", "s2c_run", "s2c_pileup_ext", "s2c_run_ext", "s2c_pileup_lean", "s2c_run_lean", "s2c_pileup_counts",
     "s2c_gather_bodies_dev", "s2c_plan_set_cus", "s2c_table_len", "s2c_table_write",
     "s2c_sites_mark", "s2c_sites_len", "s2c_sites_write",
     "s2c_runs_mark", "s2c_runs_len", "s2c_runs_write",
@@ -194,6 +203,7 @@ def _load():
         "s2c_batch_info_get": (C.c_int, [_VP, C.POINTER(BatchInfo)]),
         "s2c_batch_arrays_get": (C.c_int, [_VP, C.POINTER(BatchArrays)]),
         "s2c_batch_dense_ext_get": (C.c_int, [_VP, C.POINTER(DenseExt)]),
+        "s2c_batch_dense_lean_get": (C.c_int, [_VP, C.POINTER(DenseLean)]),
         "s2c_batch_ref_name": (C.c_char_p, [_VP, C.c_int64]),
         "s2c_batch_free": (None, [_VP]),
         "s2c_batch_shard": (C.c_int, [_VP, C.c_int64, C.c_int64, pp]),
@@ -210,6 +220,8 @@ def _load():
         "s2c_run": (C.c_int, [C.POINTER(Dev), _VP]),
         "s2c_pileup_ext": (C.c_int, [C.POINTER(Dev), C.POINTER(DenseExt), _VP]),
         "s2c_run_ext": (C.c_int, [C.POINTER(Dev), C.POINTER(DenseExt), _VP]),
+        "s2c_pileup_lean": (C.c_int, [C.POINTER(Dev), C.POINTER(DenseExt), C.POINTER(DenseLean), _VP]),
+        "s2c_run_lean": (C.c_int, [C.POINTER(Dev), C.POINTER(DenseExt), C.POINTER(DenseLean), _VP]),
         "s2c_gather_bodies_dev": (C.c_int, [_VP, C.c_int64, _VP, _VP, C.c_int64, _VP, _VP]),
         "s2c_plan_set_cus": (C.c_int, [C.c_int64]),
         "s2c_table_len": (C.c_int, [_VP, C.c_int64, _VP, C.c_int64, _VP, _VP]),

@@ -116,6 +116,14 @@ class HostBatch:
         self.dxs = _view(x.dxs, x.n_dxs, np.uint32)
         self.drare = _view(x.drare, x.n_drare * L.S2C_DPC_WORDS, np.uint32).reshape(-1, L.S2C_DPC_WORDS)
         self.dext = _view(x.dext, x.n_dext * L.S2C_DEXT_WORDS, np.uint32).reshape(-1, L.S2C_DEXT_WORDS)
+        # ... and its lean part (s2c_dense_lean): the rare pieces' op words, their offsets, each
+        # window's {first, count}; the launch's window bytes, largest lane count, plane pairs
+        y = L.DenseLean()
+        L.check(lib.s2c_batch_dense_lean_get(self._b, C.byref(y)))
+        self.rop = _view(y.rop, y.n_rop, np.uint32)
+        self.roff = _view(y.roff, y.n_roff, np.uint32)
+        self.drow = _view(y.row, y.n_row * L.S2C_DLEAN_WORDS, np.uint32).reshape(-1, L.S2C_DLEAN_WORDS)
+        self.lean_lds, self.lean_count, self.lean_pairs = int(y.lds), int(y.count_max), int(y.pairs)
         self.lp = _view(a.lp, i.n_long, np.uint32)
         self.wtile = _view(a.wtile, i.n_words, np.uint32)
         self.names = [lib.s2c_batch_ref_name(self._b, k).decode("latin-1") for k in range(i.n_refs)]

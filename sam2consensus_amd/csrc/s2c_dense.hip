@@ -1,7 +1,8 @@
 // s2c_dense.hip — k_tile_dense: shallow tiles without insertion keys (-f of one char).
 //
 // Such a tile's body is one char per position (:355-389 with no insertion columns and a
-// one-char fill), so the byte offset of position q is q: no length scan.  One wave per tile:
+// one-char fill), so the byte offset of position q is q: no length scan.  Two waves per tile
+// (WPT) share its window:
 //
 //   1. DMA     the tile's window — the op words, base planes {p0, p1} and non-ACGT plane of
 //              the short pieces starting up to kwin words before the tile (one contiguous
@@ -19,7 +20,9 @@
 //              With the windows' extension (s2c.h s2c_dense_ext, k_tile_dense<·, true>) the
 //              host has done the common piece's part: the window's run records arrive by a
 //              third DMA, the 'N' events and X-run slots as lists, and thread i takes rare
-//              piece i from the window's own list — no lean walk, no compaction.
+//              piece i from the window's own list — no lean walk, no compaction.  No op words
+//              are staged: those of the rare pieces arrive as a block of their own (s2c.h
+//              s2c_dense_lean), and the window's LDS lets nine tiles reside per CU.
 //   3. count  the G = 64 / (tile words) lanes of a word count the runs covering it — A C G T
 //              into bit-sliced Harley–Seal counters, 8 records at a time.
 //   4. vote    each lane holds 8 / G counter rows (a row = positions 8j + r, j = 0..3, one
@@ -87,23 +90,30 @@ struct DenseArgs {
     // events, X-run slots, rare pieces' records, the windows' rows; the end of the DMA source
     const uint32_t *drun, *dnev, *dxs, *drare, *dext;
     const void *drun_end;
+    // ... and its lean part (s2c.h s2c_dense_lean): the rare pieces' op words, their offsets, the
+    // windows' rows; the end of the DMA source
+    const uint32_t *rop, *roff, *drow;
+    const void *rop_end;
+    uint32_t xch_wave;   // bytes of a wave's share of the counters' exchange (the launch's plane pairs)
 };
 
 // The token walk of walk_piece (s2c_common.h: parsecigar :64-81 + maxdel :210) in 32-bit
 // window-relative coordinates (klen, len(SEQ) < 2^24; the window's query bases < 2^17),
 // without insertion events (a dense tile holds no keys).  q0: window-relative query base of
 // SEQ[0]; op words j are window-relative; run(j, gpos, len, kind, q) as in walk_piece with
-// q window-relative.
+// q window-relative.  The op word of slot j is opl[j + ob] (ob = 0: the window's op words; the
+// extension's walk reads the piece's words from its window's block of rare op words).
 template <class RunFn>
-__device__ __forceinline__ void walk_window(const uint32_t *opl, const uint2 *bql, const uint32_t *bxl, const uint4 P,
+__device__ __forceinline__ void walk_window(const uint32_t *opl, uint32_t ob, const uint2 *bql, const uint32_t *bxl, const uint4 P,
                                             uint32_t j0, uint32_t j1, uint32_t q0, bool maxdel_active, uint32_t maxdel,
                                             RunFn &&run) {
     const uint32_t slen = P.w & 0xFFFFFFu, fl = P.w >> 24;
     uint32_t j = j0;
     uint32_t ka = 0, kb = 0xFFFFFFFFu;
+    auto opw = [&](uint32_t i) { return opl[i + ob]; };   // (mod 2^32: ob may be "negative")
     if (fl & S2C_PF_RANGE) {
-        ka = opl[j];
-        kb = opl[j + 1];
+        ka = opw(j);
+        kb = opw(j + 1);
         run(j, 0u, 0u, S2C_RUN_EMPTY, 0u);
         run(j + 1, 0u, 0u, S2C_RUN_EMPTY, 0u);
         j += 2;
@@ -116,7 +126,7 @@ __device__ __forceinline__ void walk_window(const uint32_t *opl, const uint2 *bq
     if (maxdel_active) {   // :210
         uint32_t dashes = 0, start = 0;
         for (uint32_t i = j; i < j1; i++) {
-            const uint32_t w = opl[i], op = w & 15u, l = w >> 4;
+            const uint32_t w = opw(i), op = w & 15u, l = w >> 4;
             if (op_bases(op)) {
                 uint32_t take = start < slen ? min(l, slen - start) : 0u;
                 if (fl & S2C_PF_DASH) {   // '-' chars of SEQ: x = 1, p1 = 0, p0 = 1
@@ -141,10 +151,10 @@ __device__ __forceinline__ void walk_window(const uint32_t *opl, const uint2 *bq
     const uint32_t bkind = S2C_RUN_BASES | ((fl & S2C_PF_X) ? S2C_RUN_XBIT : 0u) | (drop ? S2C_RUN_DROP : 0u);
     uint32_t k = 0, start = 0;
     // the next op word read ahead of run()'s LDS writes (which the compiler must assume alias it)
-    uint32_t wn = j < j1 ? opl[j] : 0u;
+    uint32_t wn = j < j1 ? opw(j) : 0u;
     for (; j < j1; j++) {
         const uint32_t w = wn, op = w & 15u, l = w >> 4;
-        wn = opl[min(j + 1u, j1 - 1u)];
+        wn = opw(min(j + 1u, j1 - 1u));
         uint32_t rg = 0, rl = 0, rk = S2C_RUN_EMPTY, rq = 0;
         const bool bases = op_bases(op);
         if (bases || op_dash(op)) {
@@ -201,7 +211,7 @@ __device__ __forceinline__ uint2 rec_enc_b(uint32_t rs, uint32_t len, uint32_t q
     return make_uint2(rs | ((rs + len) << 16), q - rs);
 }
 
-constexpr int WGD = 64;   // one wave per tile
+constexpr int WGD = 64;   // lanes of a wave (a tile takes WPT waves)
 constexpr int GSD = 8;    // records per counting group (one Harley–Seal tree)
 // records whose geometry and plane words are in registers at once (4: 109 VGPRs, the plane
 // reads of four records in flight, no faster on C5 — the SIMD's other waves cover the wait;
@@ -449,8 +459,9 @@ struct Win {
     uint32_t tile, a, n, cb0, pf0, npc, o0, nslot, qw0, nqw, W0, nwords, lp0, nlong, dpc0;
 };
 // ... and its row of the extension (S2C_DEXT_WORDS; nslot is the window's own)
+//     and of its lean part (S2C_DLEAN_WORDS): its block of rare op words
 struct XWin {
-    uint32_t run0, nev0, nnev, xs0, nxs, rare0, nrare;
+    uint32_t run0, nev0, nnev, xs0, nxs, rare0, nrare, rop0, nrop;
 };
 template <bool EXT>
 __device__ __forceinline__ Win win_of(const DenseArgs &d, uint32_t item, XWin &xw) {
@@ -460,11 +471,14 @@ __device__ __forceinline__ Win win_of(const DenseArgs &d, uint32_t item, XWin &x
     v16i r;
     if constexpr (EXT) {
         v8i x;
-        asm volatile("s_load_dwordx16 %0, %2, 0x0\n\ts_load_dwordx8 %1, %3, 0x0\n\ts_waitcnt lgkmcnt(0)"
-                     : "=&s"(r), "=&s"(x)
-                     : "s"(uni_ptr(d.dwin + (size_t)item * S2C_DWIN_WORDS)), "s"(uni_ptr(d.dext + (size_t)item * S2C_DEXT_WORDS))
+        uint64_t y;
+        asm volatile("s_load_dwordx16 %0, %3, 0x0\n\ts_load_dwordx8 %1, %4, 0x0\n\ts_load_dwordx2 %2, %5, 0x0\n\ts_waitcnt lgkmcnt(0)"
+                     : "=&s"(r), "=&s"(x), "=&s"(y)
+                     : "s"(uni_ptr(d.dwin + (size_t)item * S2C_DWIN_WORDS)), "s"(uni_ptr(d.dext + (size_t)item * S2C_DEXT_WORDS)),
+                       "s"(uni_ptr(d.drow + (size_t)item * S2C_DLEAN_WORDS))
                      : "memory");
-        xw = XWin{(uint32_t)x[0], (uint32_t)x[2], (uint32_t)x[3], (uint32_t)x[4], (uint32_t)x[5], (uint32_t)x[6], (uint32_t)x[7]};
+        xw = XWin{(uint32_t)x[0], (uint32_t)x[2], (uint32_t)x[3], (uint32_t)x[4], (uint32_t)x[5], (uint32_t)x[6], (uint32_t)x[7],
+                  (uint32_t)y, (uint32_t)(y >> 32)};
     } else {
         xw = XWin{};
         asm volatile("s_load_dwordx16 %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)"
@@ -489,39 +503,57 @@ __device__ __forceinline__ Win win_of(const DenseArgs &d, uint32_t item, XWin &x
 }
 // The window's arrays in LDS (S2C_DENSE_BYTES layout): op words, planes (each at its
 // source's 16-byte phase, dma16), run records + RUN_PAD zero records, the walk's queues.
+// With the extension (S2C_DENSE_LEAN_BYTES layout): planes, the rare pieces' op words, run
+// records + run_pad zero records, the X-run queue of the rare pass.
 constexpr uint32_t RUN_PAD = 64;   // zero records after the last: a count group's reads past it
+// ... with the extension as many as a group reads past it: up to record nslot + 7·G
+template <int NWP, bool EXT>
+constexpr uint32_t run_pad = EXT ? (uint32_t)S2C_DENSE_LEAN_PAD(NWP) : RUN_PAD;
 struct WinLds {
-    const uint32_t *opl;
+    const uint32_t *opl;   // (with the extension: the window's block of rare op words)
     const uint2 *bql;
     uint2 *runl;
     uint32_t *q;   // [nslot + 128]: queued pieces (window index) from the front, X-run slots from the back
-                   // (with the extension: the X-run slots of the rare pass alone, a wave from either end)
+                   // (with the extension: [min(2·nrare, nslot + 128)], the X-run slots of the rare pass
+                   // alone, a wave from either end)
 };
 __device__ __forceinline__ const uint32_t *phase16(const uint8_t *region, const void *src) {
     return (const uint32_t *)(region + ((uintptr_t)src & 15));
 }
-__device__ __forceinline__ WinLds win_lds(const DenseArgs &d, const Win &v, uint8_t *buf) {
+template <int NWP, bool EXT>
+__device__ __forceinline__ WinLds win_lds(const DenseArgs &d, const Win &v, const XWin &xw, uint8_t *buf) {
     WinLds L;
-    const uint32_t *sop = d.ops + v.o0, *sbq = d.bq + 2 * (size_t)v.qw0;
-    L.opl = phase16(buf, sop);
-    buf += dma16_bytes(v.nslot);
+    const uint32_t *sop = EXT ? d.rop + xw.rop0 : d.ops + v.o0, *sbq = d.bq + 2 * (size_t)v.qw0;
+    if constexpr (!EXT) {
+        L.opl = phase16(buf, sop);
+        buf += dma16_bytes(v.nslot);
+    }
     L.bql = (const uint2 *)phase16(buf, sbq);
     buf += dma16_bytes(2 * v.nqw);
+    if constexpr (EXT) {
+        L.opl = phase16(buf, sop);
+        buf += dma16_bytes(xw.nrop);
+    }
     L.runl = (uint2 *)buf;
-    L.q = (uint32_t *)(L.runl + v.nslot + RUN_PAD);
+    L.q = (uint32_t *)(L.runl + v.nslot + run_pad<NWP, EXT>);
     return L;
 }
 // issue the LDS-DMA of window v into buf, shared by the tile's waves (completion: every wave's
 // s_waitcnt vmcnt(0), then a barrier)
 template <int WPT, bool EXT>
 __device__ __forceinline__ void win_issue(const DenseArgs &d, const Win &v, const XWin &xw, uint8_t *buf) {
-    dma16<WPT>(buf, d.ops + v.o0, v.nslot, d.ops_end);
-    buf += dma16_bytes(v.nslot);
+    if constexpr (!EXT) {
+        dma16<WPT>(buf, d.ops + v.o0, v.nslot, d.ops_end);
+        buf += dma16_bytes(v.nslot);
+    }
     dma16<WPT>(buf, d.bq + 2 * (size_t)v.qw0, 2 * v.nqw, d.bq_end);
     if constexpr (EXT) {
-        // the window's run records onto runl (its block starts 16-byte aligned: phase 0; the
-        // last 16 bytes of an odd block carry the host's zero pad record onto a RUN_PAD record)
+        // the rare pieces' op words, then the window's run records onto runl (its block starts
+        // 16-byte aligned: phase 0; the last 16 bytes of an odd block carry the host's zero pad
+        // record onto a pad record)
         buf += dma16_bytes(2 * v.nqw);
+        dma16<WPT>(buf, d.rop + xw.rop0, xw.nrop, d.rop_end);
+        buf += dma16_bytes(xw.nrop);
         dma16<WPT>(buf, d.drun + 2 * (size_t)xw.run0, 2 * v.nslot, d.drun_end);
     }
 }
@@ -532,8 +564,8 @@ __device__ __forceinline__ void win_issue(const DenseArgs &d, const Win &v, cons
 constexpr int WPT = 2;   // waves per tile (they share the window)
 constexpr int WT = WGD * WPT;     // threads per tile
 constexpr int PFN = 2;   // piece records per thread loaded with the DMA (windows of ≤ PFN·WT pieces)
-// EXT: the walk from the windows' extension (xw; Pc[0] = this thread's rare record, Pc[1].x its
-// 'N' event), the run records already in runl.
+// EXT: the walk from the windows' extension (xw; Pc[0] = this thread's rare record, Pc[1].y its
+// op words' offset in L.opl, Pc[1].x the thread's 'N' event), the run records already in runl.
 template <int NWP, bool EXT>
 __device__ __forceinline__ void dense_tile(const DenseArgs &d, const Win &v, const XWin &xw, const WinLds &L, uint32_t *dcnt,
                                            uint32_t *ncnt, uint32_t *ccnt, const uint8_t *amb, uint32_t fill0,
@@ -547,11 +579,14 @@ __device__ __forceinline__ void dense_tile(const DenseArgs &d, const Win &v, con
     (void)t_entry;
 #endif
     PROF_MARK(1);   // phase 0: entry → window landed (scalar tile loads, DMA, piece records)
-    const uint32_t lane = tid & 63, wv = tid >> 6;
-    const uint32_t w = wv * NWPW + lane / G, g = lane % G;   // tile-relative word of this lane
+    // (not const: with the extension they are formed again from the thread index after the count,
+    // so none of them holds a register through it — 96 VGPRs, five waves per SIMD)
+    uint32_t lane = tid & 63, wv = tid >> 6;
+    uint32_t w = wv * NWPW + lane / G, g = lane % G;   // tile-relative word of this lane
     const uint32_t tile = v.tile, a = v.a, n = v.n, cb0 = v.cb0, npc = v.npc, o0 = v.o0, qw0 = v.qw0;
-    const uint32_t W0 = v.W0, nwords = v.nwords, W = W0 + w;
-    const bool active = w < nwords;
+    const uint32_t W0 = v.W0, nwords = v.nwords;
+    uint32_t W = W0 + w;
+    bool active = w < nwords;
     const uint32_t K = d.kwin;
     const uint32_t pf0 = v.pf0;
     // the non-ACGT plane stays in HBM (read only for the ~14 % of runs with N / '-' in SEQ, in
@@ -619,10 +654,11 @@ __device__ __forceinline__ void dense_tile(const DenseArgs &d, const Win &v, con
     };
     // One piece that is not SIMPLE, from its compact record {c0, c1, pxv} (on: the lane holds
     // one), shared by both paths; room: the X-run entries this round may add (the old path's
-    // capacity rule; the extension's queue always has room)
-    auto rare_piece = [&](bool on, uint32_t c0, uint32_t c1, uint32_t pxv, uint32_t room) {
+    // capacity rule; the extension's queue always has room); rov: with the extension, the offset
+    // of the piece's op words in opl, the window's block of rare op words (else its op slot)
+    auto rare_piece = [&](bool on, uint32_t c0, uint32_t c1, uint32_t pxv, uint32_t room, uint32_t rov) {
         const DPiece D = dpc_dec(c0, c1);
-        const uint32_t fl = D.fl, slen = D.slen, j = D.j, q = D.q;
+        const uint32_t fl = D.fl, slen = D.slen, j = D.j, q = D.q, ro = EXT ? rov : j;
         // bases, D / N / P, bases (the deletion reads) with no maxdel count to take (the rule is
         // off, or SEQ holds no '-'): two base runs (:64-72: k = take, then l1 '-', then
         // SEQ[l : l + min(l2, len(SEQ) − l)]) and the '-' run into the byte counters unless
@@ -630,7 +666,7 @@ __device__ __forceinline__ void dense_tile(const DenseArgs &d, const Win &v, con
         bool fdel = false;
         uint32_t l = 0, l1 = 0, take = 0, t2 = 0;
         if (on && D.nops == 3u && (fl & ~(uint32_t)(S2C_PF_X | S2C_PF_DASH | S2C_PF_XFEW)) == 0u && !((fl & S2C_PF_DASH) && mda)) {
-            const uint32_t w0 = opl[j], w1 = opl[j + 1], w2 = opl[j + 2];
+            const uint32_t w0 = opl[ro], w1 = opl[ro + 1], w2 = opl[ro + 2];
             fdel = op_bases(w0 & 15u) && op_dash(w1 & 15u) && op_bases(w2 & 15u);
             l = w0 >> 4;
             l1 = w1 >> 4;
@@ -676,7 +712,7 @@ __device__ __forceinline__ void dense_tile(const DenseArgs &d, const Win &v, con
             // (walk_window's view: the global start position and len(SEQ) | flags << 24)
             const uint4 P = make_uint4((uint32_t)T0 + D.rs - (uint32_t)REC_BIAS, 0u, 0u, slen | fl << 24);
             const bool lng = (fl & S2C_PF_LONG) != 0;   // (a long piece starting here does not overlap the tile)
-            walk_window(opl, bql, bxl, P, j, j + D.nops, q, mda, d.maxdel,
+            walk_window(opl, ro - j, bql, bxl, P, j, j + D.nops, q, mda, d.maxdel,
                         [&](uint32_t jr, uint32_t gp, uint32_t rl, uint32_t kind, uint32_t rq) {
                             const uint32_t kd = (lng || kind == S2C_RUN_EMPTY) ? 0u : (kind & 3u);
                             runl[jr] = kd == S2C_RUN_BASES ? rec_enc(gp - (uint32_t)T0, rl, rq) : make_uint2(0u, 0u);
@@ -699,8 +735,12 @@ __device__ __forceinline__ void dense_tile(const DenseArgs &d, const Win &v, con
             const uint32_t i = base + tid;
             const bool on = i < xw.nrare;
             uint3 R = Pc[0];
-            if (base) R = on ? ((const uint3 *)d.drare)[xw.rare0 + i] : make_uint3(0u, 0u, 0u);   // (windows of more than WT rare pieces)
-            rare_piece(on, R.x, R.y, R.z, 0xFFFFFFFFu);
+            uint32_t ro = Pc[1].y;
+            if (base) {   // (windows of more than WT rare pieces)
+                R = on ? ((const uint3 *)d.drare)[xw.rare0 + i] : make_uint3(0u, 0u, 0u);
+                ro = on ? d.roff[xw.rare0 + i] : 0u;
+            }
+            rare_piece(on, R.x, R.y, R.z, 0xFFFFFFFFu, ro);
         }
     } else {
 #pragma unroll
@@ -741,7 +781,7 @@ __device__ __forceinline__ void dense_tile(const DenseArgs &d, const Win &v, con
             }
             // (front entries [base + 64, nslow) are still to be read: the back stays above nslow
             // until the last round, which has read every front entry)
-            rare_piece(on, c0, c1, pxv, qcap - (base + WGD < nslow ? nslow : 0u));
+            rare_piece(on, c0, c1, pxv, qcap - (base + WGD < nslow ? nslow : 0u), 0u);
         }
     }
     lds_sync();   // every run record written
@@ -769,9 +809,11 @@ __device__ __forceinline__ void dense_tile(const DenseArgs &d, const Win &v, con
     const int16_t wbias = (int16_t)(32 * w + REC_BIAS);     // the word's first position, biased (rec_enc)
     const v2s wpk = (v2s){wbias, wbias};
     const uint2 *bqw = bql + ((32 * w + REC_BIAS) >> 5);    // plane word of query y + wbias, less y >> 5
-    auto load_runs = [&](uint2 (&rv)[GSD], uint32_t gi) {
+    uint32_t ri = cw0 + g;   // first record of the next group loaded (the groups are loaded in order)
+    auto load_runs = [&](uint2 (&rv)[GSD]) {
         // (64-bit loads: two records per ds_read2_b64)
-        const unsigned long long *rb = (const unsigned long long *)(runl + min(cw0 + g + G * GSD * gi, rend));
+        const unsigned long long *rb = (const unsigned long long *)(runl + min(ri, rend));
+        ri += G * GSD;
 #pragma unroll
         for (int u = 0; u < GSD; u++) {
             unsigned long long r = rb[G * u];
@@ -835,28 +877,28 @@ __device__ __forceinline__ void dense_tile(const DenseArgs &d, const Win &v, con
     uint2 ra[GSD], rb2[GSD];
     auto trip = [&](uint32_t gi) -> bool {   // groups gi, gi + 1; false: the last group counted
         uint32_t t8a[4], t8b[4];
-        if (gi + 1 < ngrp) load_runs(rb2, gi + 1);
+        if (gi + 1 < ngrp) load_runs(rb2);
         count_group(ra, t8a, Full{});
         if (gi + 1 >= ngrp) {
 #pragma unroll
             for (int c = 0; c < 4; c++) close8(C[c], t8a[c]);
             return false;
         }
-        if (gi + 2 < ngrp) load_runs(ra, gi + 2);
+        if (gi + 2 < ngrp) load_runs(ra);
         count_group(rb2, t8b, Full{});
 #pragma unroll
         for (int c = 0; c < 4; c++) close16(C[c], t8a[c], t8b[c]);
         return true;
     };
     if (ngrp) {   // the first trip peeled: its counters start at zero (folded, no initialising moves)
-        load_runs(ra, 0);
+        load_runs(ra);
         if (trip(0))
             for (uint32_t gi = 2; gi < ngrp; gi += 2)
                 if (!trip(gi)) break;
     }
     if (half) {   // records 8·ngrp .. 8·ngrp + 3 of each lane
         uint32_t t4[4];
-        load_runs(ra, ngrp);
+        load_runs(ra);
         count_group(ra, t4, Half{});
 #pragma unroll
         for (int c = 0; c < 4; c++) close4(C[c], t4[c]);
@@ -867,6 +909,14 @@ __device__ __forceinline__ void dense_tile(const DenseArgs &d, const Win &v, con
     // runs' parts in the lane's word — bases into the counters (planes from HBM), '-' runs and
     // the N / '-' chars of SEQ into the byte counters (the host keeps a dense tile's candidate
     // runs + long runs ≤ 255 per word)
+    if constexpr (EXT) {   // the lane's indices once more (opaque: not kept from before the count)
+        uint32_t t = tid;
+        asm volatile("" : "+v"(t));
+        lane = t & 63, wv = t >> 6;
+        w = wv * NWPW + lane / G, g = lane % G;
+        W = W0 + w;
+        active = w < nwords;
+    }
     uint32_t ntr = 0;   // long-piece rounds (each adds ≤ 1 per position to a lane's counters)
     if (v.nlong) {
         const int32_t wr = (int32_t)(32 * w);   // tile-relative first position of the lane's word
@@ -955,11 +1005,14 @@ __device__ __forceinline__ void dense_tile(const DenseArgs &d, const Win &v, con
         const uint32_t part = PARTS == 2 ? (g >= 4 ? 1u : 0u) : 0u;
         const uint32_t cb = PARTS == 2 ? min(g, 7u - g) : (g % (uint32_t)SRC) * (uint32_t)CPL;
         const uint32_t src0 = wl * G + part * SRC;
-        uint2 *xp = (uint2 *)(scratch + wv * XCH_WAVE_BYTES);   // this wave's scratch
+        // this wave's scratch (with the extension: sized for the launch's plane pairs, which a
+        // lane's count here never exceeds — the host's S2C_DENSE_PAIRS over the same counts)
+        uint2 *xp = (uint2 *)(scratch + wv * (EXT ? d.xch_wave : XCH_WAVE_BYTES));
         uint32_t *vp = (uint32_t *)xp;   // the rows (aliases the planes: read before, in wave order)
-        // a lane's count ≤ its record slots + long rounds: planes 0 .. 2·NCH − 1 carry it
+        // a lane's count ≤ its record slots + long rounds: planes 0 .. 2·NCH − 1 carry it (s2c.h
+        // S2C_DENSE_SLOTS / S2C_DENSE_PAIRS: the rule the host sizes the launch's exchange by)
         const uint32_t mxc = 8 * ngrp + (half ? 4u : 0u) + ntr;
-        const uint32_t npl = 32u - (uint32_t)__builtin_clz(mxc | 1u);
+        const uint32_t nch = S2C_DENSE_PAIRS(mxc);
         auto xchg = [&](auto nch_c) {
             constexpr int NCH = decltype(nch_c)::value;   // plane pairs exchanged
 #pragma unroll
@@ -1001,9 +1054,9 @@ __device__ __forceinline__ void dense_tile(const DenseArgs &d, const Win &v, con
             }
             wave_lds_sync();
         };
-        if (npl <= 2) xchg(std::integral_constant<int, 1>{});
-        else if (npl <= 4) xchg(std::integral_constant<int, 2>{});
-        else if (npl <= 6) xchg(std::integral_constant<int, 3>{});
+        if (nch == 1) xchg(std::integral_constant<int, 1>{});
+        else if (nch == 2) xchg(std::integral_constant<int, 2>{});
+        else if (nch == 3) xchg(std::integral_constant<int, 3>{});
         else xchg(std::integral_constant<int, 4>{});
         const uint32_t *vr = vp + wl * XCH_VROW + g * RPL;
 #pragma unroll
@@ -1022,9 +1075,17 @@ __device__ __forceinline__ void dense_tile(const DenseArgs &d, const Win &v, con
     const uint32_t md16 = md | (md << 16);
     // per row: chars of the largest count, masks (one byte per position) of strict majority
     // and of "not called", the largest count m1 and coverage (bytes), in-tile bytes
-    uint32_t chr[RPL], fmk[RPL], ncm[RPL], m1b[RPL], cvb[RPL], inb[RPL];
+    // (the in-tile bytes are not kept per row: a wave inside the tile has them all, the tile's
+    // last wave forms them again where a threshold needs them — RPL registers fewer through the vote)
+    // (nor is the coverage: the one threshold class that needs it again adds the counts up)
+    uint32_t chr[RPL], fmk[RPL], ncm[RPL], m1b[RPL];
     uint32_t sc = 0;
     const bool wave_full = uni(n >= 32u * (wv * NWPW + NWPW) ? 1u : 0u) != 0u;   // (uniform)
+    auto in_tile = [&](int rr) -> uint32_t {
+        if (wave_full) return 0xFFFFFFFFu;
+        const int32_t nj = min(max(((int32_t)n - (int32_t)(32 * w + g * RPL + rr) + 7) >> 3, 0), 4);
+        return (active && nj) ? 0xFFFFFFFFu >> (32 - 8 * nj) : 0u;
+    };
 #pragma unroll
     for (int rr = 0; rr < RPL; rr++) {
         const uint32_t cA = rA[rr] - rN[rr], cC = rC[rr] - rX[rr];   // 'N' counted as A, SEQ '-' as C
@@ -1032,13 +1093,7 @@ __device__ __forceinline__ void dense_tile(const DenseArgs &d, const Win &v, con
         // in-tile positions: p = 32w + 8j + r < n
         // (bytes j < ⌈(n − pr) / 8⌉, at most 4)
         // (a wave whose words are all inside the tile — every wave of a full tile: all bytes)
-        uint32_t im = 0xFFFFFFFFu;
-        if (!wave_full) {
-            const int32_t nj = min(max(((int32_t)n - (int32_t)(32 * w + g * RPL + rr) + 7) >> 3, 0), 4);
-            im = (active && nj) ? 0xFFFFFFFFu >> (32 - 8 * nj) : 0u;
-        }
-        inb[rr] = im;
-        cvb[rr] = cv;
+        const uint32_t im = in_tile(rr);
         sc = __builtin_amdgcn_udot4(cv & im, 0x01010101u, sc, false);   // Σ cov over the tile (:357)
         // keys count << 8 | symbol ("-ACGNT" index), halves e (j = 0, 2) and o (j = 1, 3); the
         // largest key's symbol is the char wherever the count is a strict majority (elsewhere
@@ -1063,7 +1118,10 @@ __device__ __forceinline__ void dense_tile(const DenseArgs &d, const Win &v, con
     }
     const uint32_t fill4 = fill0 * 0x01010101u;
     const uint64_t ostride = (uint64_t)d.padded_len + d.n_cols;   // max(1, len(fill)) = 1
-    uint8_t *const obase = d.out + (uint64_t)a + cb0 + 32 * w + g * RPL;
+    // (a uniform base and the lane's 32-bit offset: one address register through the vote, not two)
+    uint8_t *const obase = d.out + (uint64_t)a + cb0;
+    const uint32_t olane = 32 * w + g * RPL;
+    const uint32_t wvu = uni(wv);   // (the wave's index in an SGPR: its slot of stl)
     const bool full = active && 32 * w + 32 <= n;
     // the count of symbol s at row rr, byte j (slow path: run-time indices, select chains)
     auto sel = [&](const uint32_t (&R)[RPL], uint32_t r) -> uint32_t {
@@ -1085,7 +1143,7 @@ __device__ __forceinline__ void dense_tile(const DenseArgs &d, const Win &v, con
         for (int rr = 0; rr < RPL; rr++) {
             uint32_t fm = (clsA || clsB) ? fmk[rr] & ~ncm[rr] : 0u;
             if (clsB) {   // m1·2^15 ≥ uq·cov per position (m1, cov ≤ 255: 32-bit products)
-                uint32_t ok = 0, mb = m1b[rr], cb = cvb[rr];
+                uint32_t ok = 0, mb = m1b[rr], cb = rA[rr] + rC[rr] - rX[rr] + rG[rr] + rT[rr] + rD[rr];   // (cov: 'N' inside rA)
                 asm volatile("" : "+v"(mb), "+v"(cb));   // (kept here: not hoisted for every class)
 #pragma unroll
                 for (int j = 0; j < 4; j++) {
@@ -1099,7 +1157,7 @@ __device__ __forceinline__ void dense_tile(const DenseArgs &d, const Win &v, con
             // non-'-' chars: fast chars ≠ '-' and in-tile fill chars
             const uint32_t nz = (chr[rr] ^ 0x2D2D2D2Du) & fm;   // nonzero byte ⟺ fast char ≠ '-'
             const uint32_t nzb = (((nz & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | nz) & 0x80808080u;
-            nd += (uint32_t)__popc(nzb) + d.fill_nondash * (uint32_t)__popc(ncm[rr] & inb[rr] & 0x01010101u);
+            nd += (uint32_t)__popc(nzb) + d.fill_nondash * (uint32_t)__popc(ncm[rr] & in_tile(rr) & 0x01010101u);
         }
         // the other called positions: closed form of the group-sort vote (:241-251, :359-366)
         if (ABL(64)) slow = 0;
@@ -1127,7 +1185,9 @@ __device__ __forceinline__ void dense_tile(const DenseArgs &d, const Win &v, con
             }
         }
         // rows → consecutive positions: byte j of row rr is position 8j + g·RPL + rr
-        uint8_t *dst = obase + (uint64_t)t * ostride;
+        uint32_t ol = olane;   // (an opaque copy: neither its 64-bit extension nor n − olane is carried through the vote)
+        asm volatile("" : "+v"(ol));
+        uint8_t *dst = obase + (uint64_t)t * ostride + ol;
         uint32_t cj[4];   // RPL ≤ 4 bytes of each j (RPL = 8: two halves, below)
         auto tr4 = [](uint32_t r0, uint32_t r1, uint32_t r2, uint32_t r3, uint32_t (&o)[4]) {   // 4×4 byte transpose
             const uint32_t t0 = __builtin_amdgcn_perm(r1, r0, 0x05010400u);
@@ -1165,8 +1225,7 @@ __device__ __forceinline__ void dense_tile(const DenseArgs &d, const Win &v, con
                     else body_st(dst + 8 * j, (uint8_t)cj[j]);
                 }
             } else if (active) {   // (the tile's last word; bounds kept here, not hoisted)
-                uint32_t nn = n - 32 * w - g * RPL;
-                asm volatile("" : "+v"(nn));
+                const uint32_t nn = n - ol;
 #pragma unroll
                 for (int j = 0; j < 4; j++)
 #pragma unroll
@@ -1190,9 +1249,9 @@ __device__ __forceinline__ void dense_tile(const DenseArgs &d, const Win &v, con
         }
         if (__ballot(ne != 0u)) nde |= wave_sum(ne) << 16;
         if (lane == 0) {   // this wave's share (by threshold parity: one barrier per threshold)
-            stl[t & 1][wv][0] = sc;
-            stl[t & 1][wv][1] = nde & 0xFFFFu;
-            stl[t & 1][wv][2] = nde >> 16;
+            stl[t & 1][wvu][0] = sc;
+            stl[t & 1][wvu][1] = nde & 0xFFFFu;
+            stl[t & 1][wvu][2] = nde >> 16;
         }
         lds_sync();
         if (tid == 0) {   // tile statistics (:352-397); ≤ 2048 positions: u32 partial sums
@@ -1225,11 +1284,13 @@ __device__ __forceinline__ void dense_tile(const DenseArgs &d, const Win &v, con
 #endif
 }
 
-// One wave per tile (block b → item, XCD-major: the blocks of one XCD, b ≡ x mod 8, take a
+// One workgroup of WPT waves per tile (block b → item, XCD-major: the blocks of one XCD, b ≡ x mod 8, take a
 // contiguous range of items, so neighbouring windows meet in that XCD's L2).  Everything the
 // tile needs arrives by one LDS-DMA round trip after the scalar loads of its tile record.
+// (with the extension: at most 96 VGPRs, so five waves fit a SIMD — nine tiles per CU where the
+// batch's windows and exchange leave the LDS for them; scripts/check_spills.py holds the 96)
 template <int NWP, bool EXT>
-__global__ __launch_bounds__(WT) void k_tile_dense(const DenseArgs d) {
+__global__ __launch_bounds__(WT, EXT ? 5 : 4) void k_tile_dense(const DenseArgs d) {
     extern __shared__ uint4 arena[];   // the window (S2C_DENSE_BYTES layout)
     // one byte per position (row layout): '-' (D/N/P runs, '-' of SEQ unless maxdel drops
     // the read's), 'N' of SEQ, '-' of SEQ (all: the planes count them as C, and 'N' as A)
@@ -1255,8 +1316,8 @@ __global__ __launch_bounds__(WT) void k_tile_dense(const DenseArgs d) {
     const Win v = win_of<EXT>(d, item, xw);
     uint8_t *const buf = (uint8_t *)arena;
     win_issue<WPT, EXT>(d, v, xw, buf);
-    const WinLds wl = win_lds(d, v, buf);
-    if (tid < RUN_PAD) wl.runl[v.nslot + tid] = make_uint2(0u, 0u);   // (the DMA does not write there)
+    const WinLds wl = win_lds<NWP, EXT>(d, v, xw, buf);
+    if (tid < run_pad<NWP, EXT>) wl.runl[v.nslot + tid] = make_uint2(0u, 0u);   // (the DMA does not write there)
     // with the DMA: the thread's piece records and its word's run-slot range
     constexpr int G = WGD / (NWP / WPT);
     uint3 Pc[PFN];   // (compact records: s2c.h S2C_DPC_WORDS)
@@ -1270,7 +1331,10 @@ __global__ __launch_bounds__(WT) void k_tile_dense(const DenseArgs d) {
     }
     if constexpr (EXT) {   // (dense_tile: the thread's rare record and its 'N' event; the rest in its loops)
         static_assert(PFN >= 2, "Pc[1] holds the 'N' event");
-        if (tid < xw.nrare) Pc[0] = ((const uint3 *)d.drare)[xw.rare0 + tid];
+        if (tid < xw.nrare) {
+            Pc[0] = ((const uint3 *)d.drare)[xw.rare0 + tid];
+            Pc[1].y = d.roff[xw.rare0 + tid];   // (its op words' offset in the window's block)
+        }
         if (tid < xw.nnev) Pc[1].x = d.dnev[xw.nev0 + tid];
     }
     const uint32_t w = (tid >> 6) * (NWP / WPT) + (tid & 63) / G, W = v.W0 + w, K = d.kwin;
@@ -1304,9 +1368,18 @@ __global__ __launch_bounds__(WT) void k_tile_dense(const DenseArgs d) {
 }
 
 
+// lean: the extension's launch — dynamic LDS = the largest lean window or the exchange of its
+// plane pairs (s2c.h s2c_dense_lean); else the window with its op words, the exchange of all 8 planes
 template <int NWP>
-int launch(const DenseArgs &a, bool ext, int64_t n, hipStream_t s) {
-    if (ext) k_tile_dense<NWP, true><<<(unsigned)n, WT, a.buf_bytes, s>>>(a);
+int launch(DenseArgs a, const s2c_dense_lean *lean, int64_t lds, int64_t n, hipStream_t s) {
+    static_assert(S2C_DENSE_XCH_BYTES(XCH_NCH_MAX, NWP) == WPT * XCH_WAVE_BYTES && XCH_WAVE_BYTES / XCH_NCH_MAX == 2080 &&
+                      XCH_VROW * 4 * (NWP / WPT) == 80 * NWP, "s2c.h S2C_DENSE_XCH_BYTES");
+    a.xch_wave = (uint32_t)(lean ? S2C_DENSE_XCH_BYTES(lean->pairs, NWP) / WPT : XCH_WAVE_BYTES);
+    a.buf_bytes = (uint32_t)std::max<int64_t>(lds + (WPT > 2 ? 256 * WPT : 0), (int64_t)WPT * a.xch_wave);
+#ifdef S2C_DENSE_LDS_ADD   // (a `make variant` build: the LDS share at which one tile fewer resides per CU, found by running)
+    a.buf_bytes += S2C_DENSE_LDS_ADD;
+#endif
+    if (lean) k_tile_dense<NWP, true><<<(unsigned)n, WT, a.buf_bytes, s>>>(a);
     else k_tile_dense<NWP, false><<<(unsigned)n, WT, a.buf_bytes, s>>>(a);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? S2C_OK : s2c_set_error(S2C_ERR_HIP, std::string("k_tile_dense: ") + hipGetErrorString(e));
@@ -1329,14 +1402,18 @@ extern "C" int s2c_prof_dense(unsigned long long *out, int reset) {
 }
 #endif
 
-int s2c_launch_dense(const s2c_dev *dv, const s2c_dense_ext *ext, hipStream_t st) {
+int s2c_launch_dense(const s2c_dev *dv, const s2c_dense_ext *ext, const s2c_dense_lean *lean, hipStream_t st) {
     using namespace s2c;
     if (dv->n_dense <= 0) return S2C_OK;
     if (dv->fill_len != 1) return s2c_set_error(S2C_ERR_ARG, "dense tiles need a one-char fill");
     if (dv->n_dense >= ((int64_t)1 << 31)) return s2c_set_error(S2C_ERR_LIMIT, "too many dense tiles");
     DenseArgs a;
-    // (with the windows' extension — checked by the caller, s2c_pileup_ext — dpc is not read)
+    // (with the windows' extension and its lean part — checked by the caller, s2c_pileup_lean: both
+    // or neither — dpc is not read)
     if ((!ext && !dv->dpc) || !dv->dwin) return s2c_set_error(S2C_ERR_ARG, "dense tiles need dwin and dpc (ABI 12)");
+    if ((ext != nullptr) != (lean != nullptr)) return s2c_set_error(S2C_ERR_ARG, "s2c_dense_ext and s2c_dense_lean go together");
+    a.rop = lean ? lean->rop : nullptr; a.roff = lean ? lean->roff : nullptr; a.drow = lean ? lean->row : nullptr;
+    a.rop_end = lean ? lean->rop + lean->n_rop : nullptr;
     a.drun = ext ? ext->drun : nullptr; a.dnev = ext ? ext->dnev : nullptr; a.dxs = ext ? ext->dxs : nullptr;
     a.drare = ext ? ext->drare : nullptr; a.dext = ext ? ext->dext : nullptr;
     a.drun_end = ext ? ext->drun + 2 * ext->n_drun : nullptr;
@@ -1353,16 +1430,19 @@ int s2c_launch_dense(const s2c_dev *dv, const s2c_dense_ext *ext, hipStream_t st
     a.n_thr = dv->n_thr; a.min_depth = dv->min_depth;
     a.fill = dv->fill;
     const int64_t n = dv->n_dense;
-    // LDS: the largest window of the batch (S2C_DENSE_BYTES, host plan)
-    const int64_t lds = dv->dense_lds;
-    if (lds <= 0 || lds > S2C_DENSE_LDS || (lds & 15)) return s2c_set_error(S2C_ERR_ARG, "dense_lds outside (0, S2C_DENSE_LDS] or not 16-byte aligned");
+    // LDS: the largest window of the batch (S2C_DENSE_BYTES, host plan; with the extension
+    // S2C_DENSE_LEAN_BYTES, s2c_dense_lean.lds — never more)
+    const int64_t lds = lean ? lean->lds : dv->dense_lds;
+    if (dv->dense_lds <= 0 || dv->dense_lds > S2C_DENSE_LDS || (dv->dense_lds & 15))
+        return s2c_set_error(S2C_ERR_ARG, "dense_lds outside (0, S2C_DENSE_LDS] or not 16-byte aligned");
+    if (lds <= 0 || lds > dv->dense_lds || (lds & 15))
+        return s2c_set_error(S2C_ERR_ARG, "s2c_dense_lean: lds outside (0, s2c_dev.dense_lds] or not 16-byte aligned");
     // (the window's LDS doubles as the counters' exchange after the count: at least WPT waves' share)
     // (WPT > 2: the waves' queues may take up to 64·WPT entries past S2C_DENSE_BYTES' share)
     static_assert(WPT * XCH_WAVE_BYTES == S2C_DENSE_MIN_LDS, "s2c.h S2C_DENSE_MIN_LDS (the host's occupancy plan)");
-    a.buf_bytes = (uint32_t)std::max<int64_t>(lds + (WPT > 2 ? 256 * WPT : 0), (int64_t)WPT * XCH_WAVE_BYTES);
     if constexpr (WPT <= 2) {   // (≥ 8 words per wave)
-        if (dv->tile_max <= 512) return launch<16>(a, ext != nullptr, n, st);
+        if (dv->tile_max <= 512) return launch<16>(a, lean, lds, n, st);
     }
-    if (dv->tile_max <= 1024) return launch<32>(a, ext != nullptr, n, st);
-    return launch<64>(a, ext != nullptr, n, st);   // tile_max ≤ 2048 (host plan)
+    if (dv->tile_max <= 1024) return launch<32>(a, lean, lds, n, st);
+    return launch<64>(a, lean, lds, n, st);   // tile_max ≤ 2048 (host plan)
 }

@@ -343,6 +343,10 @@ struct s2c_batch {
     // X-run slots, the rare pieces' records, and each window's {first, count} in the four
     u32buf drun, dnev, dxs, drare, dext;   // (each written whole by build_dwin)
     int64_t n_drun = 0, n_dnev = 0, n_dxs = 0, n_drare = 0;   // records / entries
+    // ... and its lean part (s2c.h s2c_dense_lean; build_dwin): the rare pieces' op words, their
+    // offsets, each window's {first, count}; the launch's window bytes, lane count and plane pairs
+    u32buf rop, roff, drow;
+    int64_t n_rop = 0, lean_lds = 0, lean_count = 0, lean_pairs = 1;
 };
 
 inline int perr(s2c_parser *p, int code, const std::string &msg) {

@@ -121,23 +121,45 @@ void build_dwin(s2c_batch *b) {
     b->dext.resize(std::max<size_t>(nd, 1) * S2C_DEXT_WORDS);
     if (!nd) std::fill(b->dext.begin(), b->dext.end(), 0u);
     const int nth = plan_threads((int64_t)nd, 64);
-    par_ranges(nth, (int64_t)nd, [&](int, int64_t i0, int64_t i1) {
+    // (the lean part, s2c.h s2c_dense_lean: each window's rare op words counted here too, and the
+    // launch's window bytes and largest lane count reduced over the windows)
+    b->drow.resize(std::max<size_t>(nd, 1) * S2C_DLEAN_WORDS);
+    std::fill(b->drow.begin(), b->drow.end(), 0u);
+    const int64_t NWP = dense_nwp_of(b->info.tile_max), G = 128 / NWP, K = b->info.kwin;
+    std::vector<int64_t> lds_t(nth, 0), cnt_t(nth, 0);
+    par_ranges(nth, (int64_t)nd, [&](int t, int64_t i0, int64_t i1) {
         for (int64_t i = i0; i < i1; i++) {
             const uint32_t *w = &b->dwin[(size_t)i * S2C_DWIN_WORDS];
             const uint32_t T0 = 32 * (w[1] >> 5), TL = 32 * ((w[2] - w[1] + 31) / 32);
-            uint32_t nev = 0, nxs = 0, nrare = 0;
+            uint32_t nev = 0, nxs = 0, nrare = 0, nrop = 0;
             for (uint32_t k = w[6]; k < w[7]; k++) {
                 const uint32_t *pc = &b->pc[4 * (size_t)k];
                 classify(pc[3] >> 24, pc[0] - T0 + 2048u, pc[3] & 0xFFFFFFu, b->px[k], TL, [&](uint32_t) { nev++; },
-                         [&] { nxs++; }, [&] { nrare++; });
+                         [&] { nxs++; }, [&] { nrare++; nrop += pc[6] - pc[2]; });
             }
             uint32_t *x = &b->dext[(size_t)i * S2C_DEXT_WORDS];
             x[1] = w[9] - w[8];
             x[3] = nev;
             x[5] = nxs;
             x[7] = nrare;
+            b->drow[(size_t)i * S2C_DLEAN_WORDS + 1] = nrop;
+            lds_t[t] = std::max<int64_t>(lds_t[t], S2C_DENSE_LEAN_BYTES((int64_t)(w[9] - w[8]), (int64_t)(w[11] - w[10]),
+                                                                         (int64_t)nrare, (int64_t)nrop, NWP));
+            // the largest count of a lane (k_tile_dense's mxc): per wave, the record slots its
+            // longest lane reads — lane 0 of the word with most candidates — plus the long rounds
+            const int64_t W0 = w[1] >> 5, nwords = (w[2] - w[1] + 31) / 32, ntr = (w[5] - w[4] + G - 1) / G;
+            for (int64_t wa = 0; wa < nwords; wa += NWP / 2) {
+                int64_t nmx = 0;
+                for (int64_t W = W0 + wa; W < W0 + std::min(wa + NWP / 2, nwords); W++)
+                    nmx = std::max<int64_t>(nmx, ((int64_t)b->rs[W + 1] - (int64_t)b->rs[std::max<int64_t>(W - K, 0)] + G - 1) / G);
+                cnt_t[t] = std::max(cnt_t[t], S2C_DENSE_SLOTS(nmx) + ntr);
+            }
         }
     });
+    b->lean_lds = *std::max_element(lds_t.begin(), lds_t.end());
+    b->lean_count = *std::max_element(cnt_t.begin(), cnt_t.end());
+    b->lean_pairs = S2C_DENSE_PAIRS(b->lean_count);
+    uint64_t nrop_tot = 0;
     uint64_t tot[4] = {0, 0, 0, 0};   // records of drun (each block from an even record: 16 bytes), dnev, dxs, drare
     for (size_t i = 0; i < nd; i++) {
         uint32_t *x = &b->dext[i * S2C_DEXT_WORDS];
@@ -145,6 +167,8 @@ void build_dwin(s2c_batch *b) {
             x[2 * c] = (uint32_t)tot[c];
             tot[c] += c == 0 ? (x[1] + 1u) & ~1u : x[2 * c + 1];
         }
+        b->drow[i * S2C_DLEAN_WORDS] = (uint32_t)nrop_tot;
+        nrop_tot += b->drow[i * S2C_DLEAN_WORDS + 1];
         if (tot[0] >= ((uint64_t)1 << 31)) throw std::runtime_error("more than 2^31 dense window run records");
     }
     b->n_drun = (int64_t)tot[0];
@@ -159,6 +183,12 @@ void build_dwin(s2c_batch *b) {
     if (!tot[1]) b->dnev[0] = 0;
     if (!tot[2]) b->dxs[0] = 0;
     if (!tot[3]) b->drare[0] = b->drare[1] = b->drare[2] = 0;
+    if (nrop_tot >= ((uint64_t)1 << 31)) throw std::runtime_error("more than 2^31 rare op words of dense windows");
+    b->n_rop = (int64_t)nrop_tot;
+    b->rop.resize(std::max<uint64_t>(nrop_tot, 1));
+    b->roff.resize(std::max<uint64_t>(tot[3], 1));
+    if (!nrop_tot) b->rop[0] = 0;
+    if (!tot[3]) b->roff[0] = 0;
     par_ranges(nth, (int64_t)nd, [&](int, int64_t i0, int64_t i1) {
         for (int64_t i = i0; i < i1; i++) {
             const uint32_t *w = &b->dwin[(size_t)i * S2C_DWIN_WORDS];
@@ -167,6 +197,7 @@ void build_dwin(s2c_batch *b) {
             uint32_t *o = &b->dpc[base[i] * S2C_DPC_WORDS];
             uint32_t *run = &b->drun[2 * (size_t)x[0]], *nev = &b->dnev[x[2]], *xs = &b->dxs[x[4]];
             uint32_t *rare = &b->drare[(size_t)x[6] * S2C_DPC_WORDS];
+            uint32_t *rop = &b->rop[b->drow[(size_t)i * S2C_DLEAN_WORDS]], *roff = &b->roff[x[6]], ro = 0;
             std::fill(run, run + 2 * (size_t)((x[1] + 1u) & ~1u), 0u);   // (every slot but the SIMPLE pieces')
             for (uint32_t k = w[6]; k < w[7]; k++, o += S2C_DPC_WORDS) {
                 const uint32_t *pc = &b->pc[4 * (size_t)k];
@@ -184,6 +215,8 @@ void build_dwin(s2c_batch *b) {
                 classify(fl, rs, slen, o[2], TL, [&](uint32_t r) { *nev++ = r; }, [&] { *xs++ = oj; },
                          [&] {
                              for (int c = 0; c < S2C_DPC_WORDS; c++) *rare++ = o[c];
+                             *roff++ = ro;
+                             for (uint32_t j = 0; j < nops; j++) rop[ro++] = b->ops[pc[2] + j];
                          });
             }
         }

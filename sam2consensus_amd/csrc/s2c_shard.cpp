@@ -240,6 +240,20 @@ extern "C" int s2c_batch_dense_ext_get(const s2c_batch *b, s2c_dense_ext *o) {
     return S2C_OK;
 }
 
+extern "C" int s2c_batch_dense_lean_get(const s2c_batch *b, s2c_dense_lean *o) {
+    if (!b || !o) return s2c_set_error(S2C_ERR_ARG, "NULL argument");
+    o->rop = b->rop.data();
+    o->roff = b->roff.data();
+    o->row = b->drow.data();
+    o->n_rop = b->n_rop;
+    o->n_roff = b->n_drare;
+    o->n_row = b->info.n_dense;
+    o->lds = b->lean_lds;
+    o->count_max = b->lean_count;
+    o->pairs = b->lean_pairs;
+    return S2C_OK;
+}
+
 extern "C" const char *s2c_batch_ref_name(const s2c_batch *b, int64_t i) {
     if (!b || i < 0 || i >= (int64_t)b->names.size()) return nullptr;
     return b->names[i].c_str();

@@ -27,7 +27,7 @@
 #include "s2c_common.h"
 
 int s2c_launch_reads(const s2c_dev *d, hipStream_t s, bool all, bool run);
-int s2c_launch_dense(const s2c_dev *d, const s2c_dense_ext *ext, hipStream_t s);
+int s2c_launch_dense(const s2c_dev *d, const s2c_dense_ext *ext, const s2c_dense_lean *lean, hipStream_t s);
 
 #ifdef S2C_PROF
 // phase clocks of k_tile (diagnostic build `make prof`, scripts/prof_tile.py): Σ over sampled
@@ -2116,7 +2116,27 @@ static int check_ext(const s2c_dev *d, const s2c_dense_ext *x) {
     return S2C_OK;
 }
 
-extern "C" int s2c_pileup_ext(const s2c_dev *d, const s2c_dense_ext *ext, void *stream) {
+// ... and its lean part (s2c.h s2c_dense_lean), after check_ext: both or neither
+static int check_lean(const s2c_dev *d, const s2c_dense_ext *x, const s2c_dense_lean *l) {
+    if (!x && !l) return S2C_OK;
+    if (!x) return s2c_set_error(S2C_ERR_ARG, "s2c_dense_lean without its s2c_dense_ext");
+    if (!l) return s2c_set_error(S2C_ERR_ARG, "s2c_dense_ext runs with its lean part: s2c_dense_lean (s2c_run_lean / s2c_pileup_lean)");
+    const struct { const uint32_t *p; int64_t n; const char *name; } a[3] = {
+        {l->rop, l->n_rop, "rop"}, {l->roff, l->n_roff, "roff"}, {l->row, l->n_row, "row"}};
+    for (const auto &e : a) {
+        if (e.n < 0 || e.n >= ((int64_t)1 << 31)) return s2c_set_error(S2C_ERR_ARG, std::string("s2c_dense_lean: bad count of ") + e.name);
+        if (e.n > 0 && !e.p) return s2c_set_error(S2C_ERR_ARG, std::string("s2c_dense_lean: ") + e.name + " is NULL with a non-zero count");
+    }
+    if (l->n_roff != x->n_drare) return s2c_set_error(S2C_ERR_ARG, "s2c_dense_lean: n_roff differs from n_drare");
+    if (l->n_row != d->n_dense) return s2c_set_error(S2C_ERR_ARG, "s2c_dense_lean: n_row differs from s2c_dev.n_dense");
+    if (d->n_dense > 0 && (l->lds <= 0 || l->lds > S2C_DENSE_LDS || (l->lds & 15)))
+        return s2c_set_error(S2C_ERR_ARG, "s2c_dense_lean: lds outside (0, S2C_DENSE_LDS] or not 16-byte aligned");
+    if (l->pairs < 1 || l->pairs > 4 || l->count_max < 0 || l->pairs < S2C_DENSE_PAIRS(l->count_max))
+        return s2c_set_error(S2C_ERR_ARG, "s2c_dense_lean: pairs outside [1, 4] or below S2C_DENSE_PAIRS(count_max)");
+    return S2C_OK;
+}
+
+extern "C" int s2c_pileup_lean(const s2c_dev *d, const s2c_dense_ext *ext, const s2c_dense_lean *lean, void *stream) {
     int rc = check_dev(d);
     if (rc) return rc;
     // dense tiles emit exactly one char per position: len(fill) must be 1, else k_tile (which
@@ -2124,18 +2144,19 @@ extern "C" int s2c_pileup_ext(const s2c_dev *d, const s2c_dense_ext *ext, void *
     if (d->n_dense > 0 && d->fill_len != 1 && !d->layers_dense)
         return s2c_set_error(S2C_ERR_ARG, "a fill of length != 1 runs the dense tiles through k_tile: their layered "
                                           "windows are needed (s2c_batch_layers_mode(b, 1))");
-    if ((rc = check_ext(d, ext))) return rc;
+    if ((rc = check_ext(d, ext)) || (rc = check_lean(d, ext, lean))) return rc;
     hipStream_t s = (hipStream_t)stream;
     const TileArgs a = tile_args(*d);
     // (the deep tiles' HBM counts are zero: before the first run by the caller, after every
     // run by s2c_consensus — s2c_dev.counts)
     if (d->n_dense > 0) {
-        rc = d->fill_len == 1 ? s2c_launch_dense(d, ext, s) : launch_tiles(a, d->tile_max, d->dense, d->n_dense, s);
+        rc = d->fill_len == 1 ? s2c_launch_dense(d, ext, lean, s) : launch_tiles(a, d->tile_max, d->dense, d->n_dense, s);
         if (rc) return rc;
     }
     return launch_tiles(a, d->tile_max, d->items, d->n_items, s);
 }
-extern "C" int s2c_pileup(const s2c_dev *d, void *stream) { return s2c_pileup_ext(d, nullptr, stream); }
+extern "C" int s2c_pileup_ext(const s2c_dev *d, const s2c_dense_ext *ext, void *stream) { return s2c_pileup_lean(d, ext, nullptr, stream); }
+extern "C" int s2c_pileup(const s2c_dev *d, void *stream) { return s2c_pileup_lean(d, nullptr, nullptr, stream); }
 
 extern "C" int s2c_consensus(const s2c_dev *d, void *stream) {
     int rc = check_dev(d);
@@ -2147,14 +2168,15 @@ extern "C" int s2c_consensus(const s2c_dev *d, void *stream) {
     return S2C_OK;
 }
 
-extern "C" int s2c_run_ext(const s2c_dev *d, const s2c_dense_ext *ext, void *stream) {
+extern "C" int s2c_run_lean(const s2c_dev *d, const s2c_dense_ext *ext, const s2c_dense_lean *lean, void *stream) {
     int rc;
-    if ((rc = check_dev(d)) || (rc = check_ext(d, ext))) return rc;   // (a bad extension: before s2c_reads launches)
+    if ((rc = check_dev(d)) || (rc = check_ext(d, ext)) || (rc = check_lean(d, ext, lean))) return rc;   // (a bad extension: before s2c_reads launches)
     if ((rc = s2c_reads(d, stream))) return rc;
-    if ((rc = s2c_pileup_ext(d, ext, stream))) return rc;
+    if ((rc = s2c_pileup_lean(d, ext, lean, stream))) return rc;
     return s2c_consensus(d, stream);
 }
-extern "C" int s2c_run(const s2c_dev *d, void *stream) { return s2c_run_ext(d, nullptr, stream); }
+extern "C" int s2c_run_ext(const s2c_dev *d, const s2c_dense_ext *ext, void *stream) { return s2c_run_lean(d, ext, nullptr, stream); }
+extern "C" int s2c_run(const s2c_dev *d, void *stream) { return s2c_run_lean(d, nullptr, nullptr, stream); }
 
 extern "C" int s2c_pileup_counts(const s2c_dev *d, void *stream) {
     int rc = check_dev(d);

@@ -11,7 +11,9 @@ ARRAYS = ("pc", "ops", "bq", "bx", "rs", "tiles", "items", "dense", "deep", "lp"
 # the dense windows' extension (s2c_dense_ext), uploaded in place of dpc: with it k_tile_dense
 # does not read the compact records (UPLOAD: what a run through the _ext entries uploads)
 EXT_ARRAYS = ("drun", "dnev", "dxs", "drare", "dext")
-UPLOAD = tuple(n for n in ARRAYS if n != "dpc") + EXT_ARRAYS
+# ... and its lean part (s2c_dense_lean: the rare pieces' op words, their offsets, the windows' rows)
+LEAN_ARRAYS = ("rop", "roff", "drow")
+UPLOAD = tuple(n for n in ARRAYS if n != "dpc") + EXT_ARRAYS + LEAN_ARRAYS
 # the workspace buffers a run writes (s2c_workspace_sizes), plus the thresholds and fill
 BUFFERS = ("runs", "ibkt", "ilong", "ilong_n", "counts", "ins_cols", "ins_chr", "tile_stats", "blk_len", "out")
 
@@ -54,3 +56,15 @@ def fill_ext(hb, arrays, n_dense=None):
     x.n_drun, x.n_dnev, x.n_dxs, x.n_drare = len(hb.drun), len(hb.dnev), len(hb.dxs), len(hb.drare)
     x.n_dext = len(hb.dext) if n_dense is None else int(n_dense)
     return x
+
+
+def fill_lean(hb, arrays, n_dense=None):
+    """The ``s2c_dense_lean`` beside it: ``arrays``: name → device address of each of LEAN_ARRAYS;
+    ``n_dense``: drow's rows when they were filtered like dwin (the scalars are the whole batch's:
+    they hold for any subset of its windows)."""
+    y = L.DenseLean()
+    y.rop, y.roff, y.row = arrays["rop"], arrays["roff"], arrays["drow"]
+    y.n_rop, y.n_roff = len(hb.rop), len(hb.roff)
+    y.n_row = len(hb.drow) if n_dense is None else int(n_dense)
+    y.lds, y.count_max, y.pairs = hb.lean_lds, hb.lean_count, hb.lean_pairs
+    return y

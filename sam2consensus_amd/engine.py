@@ -15,7 +15,7 @@ import torch
 
 from . import _lib as L
 from ._lib import lib
-from .devargs import EXT_ARRAYS, UPLOAD, fill_dev, fill_ext
+from .devargs import EXT_ARRAYS, LEAN_ARRAYS, UPLOAD, fill_dev, fill_ext, fill_lean
 from .table import TABLES
 
 
@@ -284,12 +284,17 @@ class Workspace:
             d.n_dense = int(len(keep(hb.dense, 0)))
             d.n_deep = int(((hb.deep >= t0) & (hb.deep < t1)).sum())
         self.dev = d
-        # the dense windows' extension (s2c_run_ext / s2c_pileup_ext): its rows filtered like dwin
+        # the dense windows' extension and its lean part (s2c_run_lean / s2c_pileup_lean): their rows
+        # filtered like dwin
         self.ext = fill_ext(db.hb, {name: getattr(db, name).data_ptr() for name in EXT_ARRAYS})
         if tile_range is not None:
             sel = (db.hb.dwin[:, 0] >= t0) & (db.hb.dwin[:, 0] < t1) if len(db.hb.dwin) else np.zeros(0, dtype=bool)
             self._sel["dext"] = _up(np.ascontiguousarray(db.hb.dext[sel]).reshape(-1), dev)
             self.ext.dext, self.ext.n_dext = _ptr(self._sel["dext"]), int(sel.sum())
+        self.lean = fill_lean(db.hb, {name: getattr(db, name).data_ptr() for name in LEAN_ARRAYS})
+        if tile_range is not None:
+            self._sel["drow"] = _up(np.ascontiguousarray(db.hb.drow[sel]).reshape(-1), dev)
+            self.lean.row, self.lean.n_row = _ptr(self._sel["drow"]), int(sel.sum())
 
     def stream_handle(self):
         return C.c_void_p(torch.cuda.current_stream(self.db.device).cuda_stream)
@@ -306,7 +311,7 @@ class Workspace:
 
     def pileup(self):
         self._counts_ready()
-        L.check(lib.s2c_pileup_ext(C.byref(self.dev), C.byref(self.ext), self.stream_handle()))
+        L.check(lib.s2c_pileup_lean(C.byref(self.dev), C.byref(self.ext), C.byref(self.lean), self.stream_handle()))
 
     def consensus(self):
         self._tables_held = False   # (k_consensus clears the deep tiles' insertion tables)
@@ -316,7 +321,7 @@ class Workspace:
         """reads → pileup (+ insertion columns, vote, FASTA bodies) → deep tiles (no host sync)."""
         self._counts_ready()
         self._tables_held = False
-        L.check(lib.s2c_run_ext(C.byref(self.dev), C.byref(self.ext), self.stream_handle()))
+        L.check(lib.s2c_run_lean(C.byref(self.dev), C.byref(self.ext), C.byref(self.lean), self.stream_handle()))
 
     def record_done(self):
         """An event after this workspace's launches so far on the compute stream: ``fetch(done)``

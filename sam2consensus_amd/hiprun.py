@@ -22,7 +22,7 @@ import numpy as np
 
 from . import _lib as L
 from ._lib import lib
-from .devargs import BUFFERS, EXT_ARRAYS, UPLOAD, fill_dev, fill_ext
+from .devargs import BUFFERS, EXT_ARRAYS, LEAN_ARRAYS, UPLOAD, fill_dev, fill_ext, fill_lean
 
 ALIGN = 256
 _H2D, _D2H = 1, 2                       # hipMemcpyHostToDevice, hipMemcpyDeviceToHost
@@ -197,8 +197,9 @@ class Session:
             d = fill_dev(i, addr, bufs, T, min_depth, fill,
                          getattr(hb, "maxdel_active", True), getattr(hb, "maxdel", 150), cap)
             x = fill_ext(hb, {n: addr[n] for n in EXT_ARRAYS})
+            y = fill_lean(hb, {n: addr[n] for n in LEAN_ARRAYS})
             t3 = time.perf_counter()
-            L.check(lib.s2c_run_ext(C.byref(d), C.byref(x), C.c_void_p()))
+            L.check(lib.s2c_run_lean(C.byref(d), C.byref(x), C.byref(y), C.c_void_p()))
             hip.sync()
             t4 = time.perf_counter()
             res = self._fetch(hb, i, T, fill_w, cap, bufs)

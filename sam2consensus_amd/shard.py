@@ -19,7 +19,7 @@ import numpy as np
 
 from . import _lib as L
 from .batch import HostBatch
-from .devargs import EXT_ARRAYS
+from .devargs import EXT_ARRAYS, LEAN_ARRAYS
 
 
 def tile_weights(hb):
@@ -250,7 +250,7 @@ def batch_bytes(hb):
     arrays over its word span only)."""
     return int(sum(np.asarray(hb.device_view(n)).nbytes for n in
                    ("pc", "ops", "bq", "bx", "rs", "tiles", "items", "dense", "deep", "lp", "wtile", "rlist", "ps", "px",
-                    "dwin") + EXT_ARRAYS))
+                    "dwin") + EXT_ARRAYS + LEAN_ARRAYS))
 
 
 def exchange_volumes(full, subs):

@@ -1,7 +1,8 @@
 """Fail the build when a kernel spills: reads the -Rpass-analysis=kernel-resource-usage
 remarks hipcc wrote for one source (Makefile) and exits 1 if any kernel's ScratchSize is
 not 0 (round 5: a spill of 416 bytes per lane in k_tile's walk-queue instantiation made C2
-25 % slower without any other sign).  Other compiler output is passed through."""
+25 % slower without any other sign).  It also exits 1 when a kernel is over its LDS share
+(LDS_CAP) or its VGPR budget (VGPR_CAP).  Other compiler output is passed through."""
 import re
 import sys
 
@@ -11,6 +12,9 @@ import sys
 # profiles/r06/d1_*, d2_*) and 54,560 (round 5) bytes ran C2 40-47 % slower with no other sign
 # (the occupancy remark does not count the CU's reserved LDS or its allocation granules)
 LDS_CAP = {"k_tileILi8E": 53536, "k_tileILi16E": 53536, "k_tileILi32E": 81920, "k_tileILi64E": 81920}
+# k_tile_dense<16 | 32 | 64, true> (the dense windows' extension): five waves per SIMD, i.e. nine
+# two-wave tiles per CU, need at most 96 VGPRs.
+VGPR_CAP = {"k_tile_denseILi16ELb1E": 96, "k_tile_denseILi32ELb1E": 96, "k_tile_denseILi64ELb1E": 96}
 
 
 def main(path):
@@ -27,6 +31,13 @@ def main(path):
             m = re.search(r"ScratchSize \[bytes/lane\]: (\d+)", ln)
             if m and int(m.group(1)) > 0:
                 bad.append((name, int(m.group(1))))
+            m = re.search(r" VGPRs: (\d+)", ln)
+            if m and name:
+                for k, cap in VGPR_CAP.items():
+                    if k in name and int(m.group(1)) > cap:
+                        sys.stderr.write("error: kernel %s takes %s VGPRs, over the %d that keep its waves per SIMD\n"
+                                         % (name, m.group(1), cap))
+                        bad.append((name, -1))
             m = re.search(r"LDS Size \[bytes/block\]: (\d+)", ln)
             if m and name:
                 for k, cap in LDS_CAP.items():
