@@ -141,13 +141,16 @@ int s2c_layout(int64_t *out, int n);
 #define S2C_DWIN_WORDS   16  /* dense item's window {tile, a, b, cb0, lp0, lp1, pf0, pf1, o0, o1, qw0, qw1, dpc0, 0, 0, 0}:
                                 the words of its tile record k_tile_dense needs, in item order (one
                                 16-dword scalar load per tile instead of item → tile → record); dpc0 (ABI 12):
-                                the first of its window's compact piece records (s2c_batch_arrays.dpc) */
-/* k_tile_dense's compact piece records (ABI 12): one per piece of each dense item's window, in
-   window order, 3 words {rs | qh' << 12 | nops << 25, oj | len(SEQ) << 13 | flags << 24, px}:
+                                the first of its window's compact piece records (s2c_batch_arrays.dpc),
+                                which the kernel no longer reads */
+/* The compact piece record (ABI 12), the format of the rare pieces' records k_tile_dense walks
+   (s2c_dense_ext.drare): 3 words {rs | qh' << 12 | nops << 25, oj | len(SEQ) << 13 | flags << 24, px}:
    rs = start position − 32·(first tile word) + 2048 (12 bits), qh' = qh − 2·qw0 (13 bits),
    nops = op slots of the piece (7 bits), oj = op slot − o0 (13 bits), len(SEQ) (11 bits), the
    piece's flags and its px word.  A tile whose window holds a piece beyond these fields
-   (len(SEQ) > S2C_DPC_SLEN_MAX, more than S2C_DPC_NOPS_MAX op slots, kwin > 64) is not dense. */
+   (len(SEQ) > S2C_DPC_SLEN_MAX, more than S2C_DPC_NOPS_MAX op slots, kwin > 64) is not dense.
+   The host still keeps one such record per piece of each dense item's window, in window order
+   (s2c_batch_arrays.dpc, from which it writes the extension); no kernel reads that array. */
 #define S2C_DPC_WORDS     3
 #define S2C_DPC_SLEN_MAX  2047
 #define S2C_DPC_NOPS_MAX  127
@@ -155,19 +158,22 @@ int s2c_layout(int64_t *out, int n);
 /* insertion columns per tile k_tile's epilogue holds in LDS, by words per tile */
 #define S2C_LDS_COLS(nwp) ((nwp) <= 16 ? 640 : ((nwp) == 32 ? 448 : 192))
 #define S2C_DENSE_LDS 32768  /* bytes of LDS a dense tile's window may take (two waves per tile share it) */
-/* LDS bytes of a dense tile's window of ns op slots and nq base plane words: op words and
-   planes {p0, p1} (each 16-byte aligned with 16 bytes of slack: the 16-byte LDS-DMA starts
-   at the boundary below the source), run records, the walk's queues (64 entries per wave and
-   walk iteration: ≤ pieces + 128).  Device arrays must be
-   readable up to their end rounded up to 16 bytes. */
+/* The host's plan rule for which tiles are dense: a tile whose window of ns op slots and nq
+   base plane words has S2C_DENSE_BYTES(ns, nq) ≤ S2C_DENSE_LDS may be.  (It was the LDS layout
+   of a walk that staged the window's op words — op words and planes {p0, p1}, run records,
+   queues of ≤ pieces + 128 entries; it is no kernel's layout any more, and bounds the one
+   below.)  Device arrays must be readable up to their end rounded up to 16 bytes. */
 #define S2C_DENSE_BYTES(ns, nq) (((4 * (ns) + 30) & ~15) + ((8 * (nq) + 30) & ~15) + ((12 * (ns) + 1024 + 15) & ~15))
-/* the dense kernel's dynamic LDS is at least this: after the count its two waves' counter
-   exchange (8,320 bytes each) reuses the window's LDS — the host's occupancy plan counts it */
+/* the host's occupancy plan counts at least this much dynamic LDS per dense tile: its two
+   waves' counter exchange at all four plane pairs (8,320 bytes each), which reuses the window's
+   LDS after the count (a launch takes S2C_DENSE_XCH_BYTES of its own pairs, never more) */
 #define S2C_DENSE_MIN_LDS 16640
-/* The window of the extension's walk (s2c_dense_lean): no op words but those of its rare pieces
-   (nrop words), planes, run records + pad zero records (8·G, G = 128 / words per tile: what a
-   count group reads past the last), the X-run queue of min(2·nrare, ns + 128) entries.  Never
-   above S2C_DENSE_BYTES(ns, nq) less the op words' share (nrop ≤ ns, pad ≤ 64). */
+/* The window of k_tile_dense in LDS (s2c_dense_lean): planes {p0, p1} and the op words of its
+   rare pieces (nrop words; each 16-byte aligned with 16 bytes of slack: the 16-byte LDS-DMA
+   starts at the boundary below the source), run records + pad zero records (8·G, G = 128 /
+   words per tile: what a count group reads past the last), the X-run queue of min(2·nrare,
+   ns + 128) entries.  Never above S2C_DENSE_BYTES(ns, nq) less its op words' share (nrop ≤ ns,
+   pad ≤ 64). */
 #define S2C_DENSE_LEAN_PAD(nwp) (1024 / (nwp))
 #define S2C_DENSE_LEAN_BYTES(ns, nq, nrare, nrop, nwp)                                                      \
     ((((8 * (nq) + 30) & ~15) + ((4 * (nrop) + 30) & ~15) + 8 * ((ns) + S2C_DENSE_LEAN_PAD(nwp)) +      \
@@ -416,8 +422,8 @@ int  s2c_batch_layers_mode(s2c_batch *b, int with_dense);
 int  s2c_batch_info_get(const s2c_batch *b, s2c_batch_info *out);
 int  s2c_batch_arrays_get(const s2c_batch *b, s2c_batch_arrays *out);
 
-/* The dense windows' extension: what k_tile_dense's walk would derive from each window's compact
- * piece records (dpc), written once by the host where it writes dpc.  Five arrays of u32 words,
+/* The dense windows' extension: what k_tile_dense walks from, derived from each window's compact
+ * piece records (dpc) and written once by the host where it writes dpc.  Five arrays of u32 words,
  * a row of dext per dense item (in dwin's order: filter dext's rows as dwin's):
  *   drun   [n_drun][2]  run records.  Window i's block is records [dext[i][0], + nslot) — one per
  *          op slot of the window (nslot = o1 − o0), in slot order, the block's first record at an
@@ -436,14 +442,14 @@ int  s2c_batch_arrays_get(const s2c_batch *b, s2c_batch_arrays *out);
  *   dext   [n_dext][S2C_DEXT_WORDS]  {drun0, nslot, dnev0, n, dxs0, n, drare0, n} per dense item.
  * s2c_batch_dense_ext_get fills the struct with host pointers into the batch (valid until
  * s2c_batch_free; an empty array has a valid pointer and count 0); the same struct with device
- * pointers is the argument of s2c_run_ext / s2c_pileup_ext. */
+ * pointers is an argument of s2c_run_lean / s2c_pileup_lean. */
 #define S2C_DEXT_WORDS 8
 typedef struct {
     const uint32_t *drun, *dnev, *dxs, *drare, *dext;
     int64_t n_drun, n_dnev, n_dxs, n_drare, n_dext;   /* records / entries / rows (not words) */
 } s2c_dense_ext;
 int  s2c_batch_dense_ext_get(const s2c_batch *b, s2c_dense_ext *out);
-/* What the extension's walk needs besides (round 9): with it k_tile_dense stages no op words.
+/* What the walk needs besides (round 9): k_tile_dense stages no op words but these.
  *   rop    [n_rop]     the op words of every window's rare pieces, in drare's order: window i's
  *          block is words [row[i][0], + row[i][1]), brought to LDS with the window's other DMAs.
  *   roff   [n_roff]    per record of drare (n_roff = n_drare) the offset of its op words in its
@@ -554,7 +560,8 @@ typedef struct {
     int64_t   layers_built;    /* the batch's info.layers_built: every launch with work items refuses 0 */
     const uint32_t *dwin;      /* [n_dense][S2C_DWIN_WORDS] s2c_batch_arrays.dwin, filtered like dense */
     const uint32_t *lpx;       /* [n_lpieces] s2c_batch_arrays.lpx (ABI 11; required with n_layers > 0) */
-    const uint32_t *dpc;       /* [n_dpc][S2C_DPC_WORDS] s2c_batch_arrays.dpc (ABI 12; required with n_dense > 0) */
+    const uint32_t *dpc;       /* no longer read (may be NULL): it was s2c_batch_arrays.dpc on the device (ABI 12).
+                                  The field, the host's dpc array and dwin's word 12 go at the next ABI bump. */
     int64_t   walk_queue;         /* (ABI 13) the batch's info.walk_queue (k_tile's variant) */
     int64_t   tile_events;        /* (ABI 13) the batch's info.tile_events (who records the finish tiles'
                                      events: must match the batch's rlist run prefix) */
@@ -585,22 +592,21 @@ int s2c_pileup(const s2c_dev *d, void *stream);
 int s2c_consensus(const s2c_dev *d, void *stream);
 /* all three, in order, on one stream (graph-capturable: no allocation, no sync) */
 int s2c_run(const s2c_dev *d, void *stream);
-/* s2c_pileup / s2c_run with the dense windows' extension (s2c_dense_ext, device pointers; dext
- * filtered like dwin): k_tile_dense takes each window's run records by LDS-DMA from drun and
- * walks only the pieces of drare, instead of deriving both from dpc — the same results.  ext =
- * NULL is s2c_pileup / s2c_run; with an extension s2c_dev.dpc is not read and may be NULL.
- * Since round 9 the extension runs through the _lean entries below; these two keep its checks.
- * S2C_ERR_ARG before any launch (after s2c_dev's own checks): a NULL array with a non-zero count,
- * a negative count, drun not 16-byte aligned, or n_dext != s2c_dev.n_dense. */
-int s2c_pileup_ext(const s2c_dev *d, const s2c_dense_ext *ext, void *stream);
-int s2c_run_ext(const s2c_dev *d, const s2c_dense_ext *ext, void *stream);
-/* (round 9) The extension's walk reads its rare pieces' op words from s2c_dense_lean, device
- * pointers with row filtered like dwin, and sizes its launch by it: s2c_pileup_lean / s2c_run_lean
- * are the entries that run it.  ext = lean = NULL is s2c_pileup / s2c_run; an extension without
- * its lean part (the _ext entries with ext != NULL included) is S2C_ERR_ARG, after the checks
- * above; so are a NULL array with a non-zero count, a negative count, n_roff != n_drare, n_row
- * != s2c_dev.n_dense, lds outside (0, S2C_DENSE_LDS] or not a 16-byte multiple, pairs outside
- * [1, 4] or below S2C_DENSE_PAIRS(count_max). */
+/* s2c_pileup / s2c_run with the dense windows' extension (s2c_dense_ext and s2c_dense_lean,
+ * device pointers; dext and row filtered like dwin): the entries that launch k_tile_dense.  It
+ * takes each window's run records by LDS-DMA from drun, walks only the pieces of drare with
+ * their op words from rop, and sizes its launch by lean.  s2c_dev.dpc is not read.
+ * S2C_ERR_ARG before any launch, in this order after s2c_dev's own checks:
+ *   ext    a NULL array with a non-zero count, a negative count, drun not 16-byte aligned, or
+ *          n_dext != s2c_dev.n_dense;
+ *   lean   one of ext / lean without the other, a NULL array with a non-zero count, a negative
+ *          count, n_roff != n_drare, n_row != s2c_dev.n_dense, lds outside (0, S2C_DENSE_LDS] or
+ *          not a 16-byte multiple, pairs outside [1, 4] or below S2C_DENSE_PAIRS(count_max);
+ *   a batch with dense tiles and a one-char fill — one that launches k_tile_dense — without
+ *          the extension (in s2c_run_lean before s2c_reads launches).
+ * ext = lean = NULL is s2c_pileup / s2c_run: for batches that launch no k_tile_dense (n_dense
+ * = 0, or a fill of length != 1 with the dense tiles' layers, where k_tile takes them); on any
+ * other they return that last refusal. */
 int s2c_pileup_lean(const s2c_dev *d, const s2c_dense_ext *ext, const s2c_dense_lean *lean, void *stream);
 int s2c_run_lean(const s2c_dev *d, const s2c_dense_ext *ext, const s2c_dense_lean *lean, void *stream);
 

@@ -76,7 +76,7 @@ class BatchArrays(C.Structure):
 
 class DenseExt(C.Structure):
     """Mirror of ``s2c_dense_ext`` (include/s2c.h): the dense windows' extension, host pointers
-    from ``s2c_batch_dense_ext_get`` or device pointers for ``s2c_run_ext`` / ``s2c_pileup_ext``."""
+    from ``s2c_batch_dense_ext_get`` or device pointers for ``s2c_run_lean`` / ``s2c_pileup_lean``."""
     _fields_ = [(n, C.c_void_p) for n in ("drun", "dnev", "dxs", "drare", "dext")] + \
         [(n, C.c_int64) for n in ("n_drun", "n_dnev", "n_dxs", "n_drare", "n_dext")]
 
@@ -135,7 +135,7 @@ EXPORTS = [
     "s2c_parser_blob_copy", "s2c_parser_unpack",
     "s2c_batch_layers", "s2c_batch_layers_mode", "s2c_batch_info_get", "s2c_batch_arrays_get", "s2c_batch_dense_ext_get", "s2c_batch_dense_lean_get", "s2c_batch_ref_name", "s2c_batch_free", "s2c_batch_shard",
     "s2c_parsecigar", "s2c_synth_feed", "s2c_synth_write",
-    "s2c_workspace_sizes", "s2c_reads", "s2c_pileup", "s2c_consensus", "s2c_run", "s2c_pileup_ext", "s2c_run_ext", "s2c_pileup_lean", "s2c_run_lean", "s2c_pileup_counts",
+    "s2c_workspace_sizes", "s2c_reads", "s2c_pileup", "s2c_consensus", "s2c_run", "s2c_pileup_lean", "s2c_run_lean", "s2c_pileup_counts",
     "s2c_gather_bodies_dev", "s2c_plan_set_cus", "s2c_table_len", "s2c_table_write",
     "s2c_sites_mark", "s2c_sites_len", "s2c_sites_write",
     "s2c_runs_mark", "s2c_runs_len", "s2c_runs_write",
@@ -218,8 +218,6 @@ def _load():
         "s2c_pileup_counts": (C.c_int, [C.POINTER(Dev), _VP]),
         "s2c_consensus": (C.c_int, [C.POINTER(Dev), _VP]),
         "s2c_run": (C.c_int, [C.POINTER(Dev), _VP]),
-        "s2c_pileup_ext": (C.c_int, [C.POINTER(Dev), C.POINTER(DenseExt), _VP]),
-        "s2c_run_ext": (C.c_int, [C.POINTER(Dev), C.POINTER(DenseExt), _VP]),
         "s2c_pileup_lean": (C.c_int, [C.POINTER(Dev), C.POINTER(DenseExt), C.POINTER(DenseLean), _VP]),
         "s2c_run_lean": (C.c_int, [C.POINTER(Dev), C.POINTER(DenseExt), C.POINTER(DenseLean), _VP]),
         "s2c_gather_bodies_dev": (C.c_int, [_VP, C.c_int64, _VP, _VP, C.c_int64, _VP, _VP]),

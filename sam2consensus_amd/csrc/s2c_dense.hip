@@ -4,25 +4,21 @@
 // one-char fill), so the byte offset of position q is q: no length scan.  Two waves per tile
 // (WPT) share its window:
 //
-//   1. DMA     the tile's window — the op words, base planes {p0, p1} and non-ACGT plane of
-//              the short pieces starting up to kwin words before the tile (one contiguous
-//              range each) — into LDS by buffer LDS-DMA with SGPR offsets (no per-lane address
-//              arithmetic); the lane's piece records into registers.
-//   2. walk    one lane per piece.  The common piece — one M / = / X token, no range, prefix
-//              or long flag, no '-' in SEQ (S2C_PF_SIMPLE) — is one run of `take` bases
-//              (parsecigar :64-69) straight from its record, its one or two 'N' added from the
-//              listed offsets; every other piece is compacted into the wave's queue and handled
-//              afterwards with all lanes busy: the deletion reads (bases, D / N / P, bases) by
-//              two base runs and a '-' range, the rest (I / S / H tokens, wrap ranges, '-' chars
-//              in SEQ) by the general parsecigar + maxdel walk (:46-82, :210).  Runs of reads
-//              holding other N / '-' chars are queued too: their SEQ chars go into the
-//              per-position byte counters in one dense pass.
-//              With the windows' extension (s2c.h s2c_dense_ext, k_tile_dense<·, true>) the
-//              host has done the common piece's part: the window's run records arrive by a
-//              third DMA, the 'N' events and X-run slots as lists, and thread i takes rare
-//              piece i from the window's own list — no lean walk, no compaction.  No op words
-//              are staged: those of the rare pieces arrive as a block of their own (s2c.h
-//              s2c_dense_lean), and the window's LDS lets nine tiles reside per CU.
+//   1. DMA     the tile's window — the base planes {p0, p1} of the short pieces starting up to
+//              kwin words before the tile, the rare pieces' op words and the window's run
+//              records (one contiguous range each; s2c.h s2c_dense_ext / s2c_dense_lean) — into
+//              LDS by buffer LDS-DMA with SGPR offsets (no per-lane address arithmetic); the
+//              thread's rare record and 'N' event into registers.
+//   2. walk    the host has done the common piece's part — one M / = / X token, no range,
+//              prefix or long flag, no '-' in SEQ (S2C_PF_SIMPLE) is one run of `take` bases
+//              (parsecigar :64-69), its record already among the window's run records, its one
+//              or two 'N' in the window's list of 'N' events, the slot of a run holding other
+//              N / '-' chars in the list of X-run slots.  Thread i takes rare piece i from the
+//              window's own list: the deletion reads (bases, D / N / P, bases) by two base runs
+//              and a '-' range, the rest (I / S / H tokens, wrap ranges, '-' chars in SEQ) by
+//              the general parsecigar + maxdel walk (:46-82, :210).  The SEQ chars of the X
+//              runs go into the per-position byte counters in one dense pass.  The window's
+//              own op words are not staged, and its LDS lets nine tiles reside per CU.
 //   3. count  the G = 64 / (tile words) lanes of a word count the runs covering it — A C G T
 //              into bit-sliced Harley–Seal counters, 8 records at a time.
 //   4. vote    each lane holds 8 / G counter rows (a row = positions 8j + r, j = 0..3, one
@@ -48,7 +44,7 @@
 // (one tile in 64) of the s_memtime deltas of each phase
 __device__ unsigned long long g_prof[16];
 __device__ uint32_t g_abl;   // ablation bits (timing only; results wrong): 1 events, 2 count, 4 walk, 8 vote, 64 slow votes,
-                             // 16 queued walk, 32 N / '-' events
+                             // 16 rare pieces' walk, 32 N / '-' events
 #define ABL(b) ((g_abl & (b)) != 0)
 #define PROF_MARK(i)                                                                               \
     do {                                                                                           \
@@ -76,18 +72,22 @@ __constant__ __attribute__((aligned(16))) uint8_t c_amb[64] = {
 };
 
 struct DenseArgs {
-    const uint32_t *rs, *pc, *ops, *bq, *bx, *tiles, *items, *lp, *dwin, *dpc;
+    // (pc, ops: the long pieces' records and op words, walked from HBM.  dpc_slot and
+    // ops_end_slot are neither set nor read: they hold the places of the compact records and of
+    // the op words' DMA end, so the kernels' argument loads — and with them their scalar register
+    // numbers — stay as they were; they go when s2c_dev.dpc does)
+    const uint32_t *rs, *pc, *ops, *bq, *bx, *tiles, *items, *lp, *dwin, *dpc_slot;
     const double *thresholds;
     uint64_t *tile_stats, *blk_len;
     uint8_t *out;
     uint32_t padded_len, n_cols, n_tiles, kwin, fill_nondash, maxdel_active, maxdel, n_items;
-    uint32_t word_lo;               // rs holds entries word_lo .. (s2c_dev, ABI 13)
-    const void *ops_end, *bq_end;   // ends of the DMA sources
-    uint32_t buf_bytes;                                        // the window's LDS (16-byte multiple)
+    uint32_t word_lo;                    // rs holds entries word_lo .. (s2c_dev, ABI 13)
+    const void *ops_end_slot, *bq_end;   // end of the planes' DMA source
+    uint32_t buf_bytes;                  // the window's LDS (16-byte multiple)
     int32_t n_thr, min_depth;
     const uint8_t *fill;   // the one -f char
-    // the windows' extension (s2c.h s2c_dense_ext; k_tile_dense<·, true>): run records, 'N'
-    // events, X-run slots, rare pieces' records, the windows' rows; the end of the DMA source
+    // the windows' extension (s2c.h s2c_dense_ext): run records, 'N' events, X-run slots, rare
+    // pieces' records, the windows' rows; the end of the DMA source
     const uint32_t *drun, *dnev, *dxs, *drare, *dext;
     const void *drun_end;
     // ... and its lean part (s2c.h s2c_dense_lean): the rare pieces' op words, their offsets, the
@@ -101,8 +101,8 @@ struct DenseArgs {
 // window-relative coordinates (klen, len(SEQ) < 2^24; the window's query bases < 2^17),
 // without insertion events (a dense tile holds no keys).  q0: window-relative query base of
 // SEQ[0]; op words j are window-relative; run(j, gpos, len, kind, q) as in walk_piece with
-// q window-relative.  The op word of slot j is opl[j + ob] (ob = 0: the window's op words; the
-// extension's walk reads the piece's words from its window's block of rare op words).
+// q window-relative.  The op word of slot j is opl[j + ob]: opl is the window's block of rare
+// op words, ob the offset of the piece's words there less its first slot.
 template <class RunFn>
 __device__ __forceinline__ void walk_window(const uint32_t *opl, uint32_t ob, const uint2 *bql, const uint32_t *bxl, const uint4 P,
                                             uint32_t j0, uint32_t j1, uint32_t q0, bool maxdel_active, uint32_t maxdel,
@@ -182,9 +182,9 @@ struct DenseMem {
     __device__ __forceinline__ uint32_t x(uint64_t w) const { return bx[w]; }
 };
 
-// A compact piece record of the item's window (s2c.h S2C_DPC_WORDS; ABI 12) decoded: rs = its
-// start relative to the tile's first word + REC_BIAS, q = query base of SEQ[0] in the window's
-// planes, its op slots [j, j + nops) in the window, len(SEQ), flags (x: word 0, y: word 1)
+// A rare piece's record (drare; s2c.h S2C_DPC_WORDS) decoded: rs = its start relative to the
+// tile's first word + REC_BIAS, q = query base of SEQ[0] in the window's planes, its op slots
+// [j, j + nops) in the window, len(SEQ), flags (x: word 0, y: word 1)
 struct DPiece {
     uint32_t rs, q, nops, j, slen, fl;
 };
@@ -192,7 +192,7 @@ __device__ __forceinline__ DPiece dpc_dec(uint32_t c0, uint32_t c1) {
     return DPiece{c0 & 0xFFFu, 16u * ((c0 >> 12) & 0x1FFFu), c0 >> 25, c1 & 0x1FFFu, (c1 >> 13) & 0x7FFu, c1 >> 24};
 }
 // FASTA body stores (written once, fetched by the host): nontemporal (−1.2 % on C5,
-// profiles/r05/v6_nt_loads_stores_ab.txt; the same policy on the compact records' loads cost +2 %)
+// profiles/r05/v6_nt_loads_stores_ab.txt)
 template <class T>
 __device__ __forceinline__ void body_st(T *p, T v) {
     if constexpr (std::is_same_v<T, uint2>) {
@@ -201,10 +201,6 @@ __device__ __forceinline__ void body_st(T *p, T v) {
     } else {
         __builtin_nontemporal_store(v, p);
     }
-}
-// (a 3-vector takes 16 bytes: the record is addressed by dwords, 3 per record, 4-byte aligned)
-__device__ __forceinline__ uint3 dpc_load(const DenseArgs &d, uint32_t i) {
-    return ((const uint3 *)d.dpc)[i];
 }
 // rec_enc from a biased start (rs = tile-relative start + REC_BIAS)
 __device__ __forceinline__ uint2 rec_enc_b(uint32_t rs, uint32_t len, uint32_t q) {
@@ -456,34 +452,27 @@ __device__ __forceinline__ uint32_t byte_bits(uint32_t m) { return ((m & 0x80808
 
 // A tile's window (uniform values from its tile record; S2C_TILE_WORDS layout)
 struct Win {
-    uint32_t tile, a, n, cb0, pf0, npc, o0, nslot, qw0, nqw, W0, nwords, lp0, nlong, dpc0;
+    uint32_t tile, a, n, cb0, pf0, npc, o0, nslot, qw0, nqw, W0, nwords, lp0, nlong;
 };
 // ... and its row of the extension (S2C_DEXT_WORDS; nslot is the window's own)
 //     and of its lean part (S2C_DLEAN_WORDS): its block of rare op words
 struct XWin {
     uint32_t run0, nev0, nnev, xs0, nxs, rare0, nrare, rop0, nrop;
 };
-template <bool EXT>
 __device__ __forceinline__ Win win_of(const DenseArgs &d, uint32_t item, XWin &xw) {
     Win v;
     // the item's window (S2C_DWIN_WORDS, built by the host from the tile record) in one
-    // scalar round trip, the extension's row beside it
+    // scalar round trip, the extension's rows beside it
     v16i r;
-    if constexpr (EXT) {
-        v8i x;
-        uint64_t y;
-        asm volatile("s_load_dwordx16 %0, %3, 0x0\n\ts_load_dwordx8 %1, %4, 0x0\n\ts_load_dwordx2 %2, %5, 0x0\n\ts_waitcnt lgkmcnt(0)"
-                     : "=&s"(r), "=&s"(x), "=&s"(y)
-                     : "s"(uni_ptr(d.dwin + (size_t)item * S2C_DWIN_WORDS)), "s"(uni_ptr(d.dext + (size_t)item * S2C_DEXT_WORDS)),
-                       "s"(uni_ptr(d.drow + (size_t)item * S2C_DLEAN_WORDS))
-                     : "memory");
-        xw = XWin{(uint32_t)x[0], (uint32_t)x[2], (uint32_t)x[3], (uint32_t)x[4], (uint32_t)x[5], (uint32_t)x[6], (uint32_t)x[7],
-                  (uint32_t)y, (uint32_t)(y >> 32)};
-    } else {
-        xw = XWin{};
-        asm volatile("s_load_dwordx16 %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)"
-                     : "=s"(r) : "s"(uni_ptr(d.dwin + (size_t)item * S2C_DWIN_WORDS)) : "memory");
-    }
+    v8i x;
+    uint64_t y;
+    asm volatile("s_load_dwordx16 %0, %3, 0x0\n\ts_load_dwordx8 %1, %4, 0x0\n\ts_load_dwordx2 %2, %5, 0x0\n\ts_waitcnt lgkmcnt(0)"
+                 : "=&s"(r), "=&s"(x), "=&s"(y)
+                 : "s"(uni_ptr(d.dwin + (size_t)item * S2C_DWIN_WORDS)), "s"(uni_ptr(d.dext + (size_t)item * S2C_DEXT_WORDS)),
+                   "s"(uni_ptr(d.drow + (size_t)item * S2C_DLEAN_WORDS))
+                 : "memory");
+    xw = XWin{(uint32_t)x[0], (uint32_t)x[2], (uint32_t)x[3], (uint32_t)x[4], (uint32_t)x[5], (uint32_t)x[6], (uint32_t)x[7],
+              (uint32_t)y, (uint32_t)(y >> 32)};
     v.tile = (uint32_t)r[0];
     v.a = (uint32_t)r[1];
     v.n = (uint32_t)r[2] - v.a;
@@ -496,66 +485,49 @@ __device__ __forceinline__ Win win_of(const DenseArgs &d, uint32_t item, XWin &x
     v.nslot = (uint32_t)r[9] - v.o0;
     v.qw0 = (uint32_t)r[10];
     v.nqw = (uint32_t)r[11] - v.qw0;
-    v.dpc0 = (uint32_t)r[12];
     v.W0 = v.a >> 5;
     v.nwords = (v.n + 31) / 32;
     return v;
 }
-// The window's arrays in LDS (S2C_DENSE_BYTES layout): op words, planes (each at its
-// source's 16-byte phase, dma16), run records + RUN_PAD zero records, the walk's queues.
-// With the extension (S2C_DENSE_LEAN_BYTES layout): planes, the rare pieces' op words, run
-// records + run_pad zero records, the X-run queue of the rare pass.
-constexpr uint32_t RUN_PAD = 64;   // zero records after the last: a count group's reads past it
-// ... with the extension as many as a group reads past it: up to record nslot + 7·G
-template <int NWP, bool EXT>
-constexpr uint32_t run_pad = EXT ? (uint32_t)S2C_DENSE_LEAN_PAD(NWP) : RUN_PAD;
+// The window's arrays in LDS (S2C_DENSE_LEAN_BYTES layout): planes, the rare pieces' op words
+// (each at its source's 16-byte phase, dma16), run records + run_pad zero records, the X-run
+// queue of the rare pass.
+// zero records after the last, as many as a count group reads past it: up to record nslot + 7·G
+template <int NWP>
+constexpr uint32_t run_pad = (uint32_t)S2C_DENSE_LEAN_PAD(NWP);
 struct WinLds {
-    const uint32_t *opl;   // (with the extension: the window's block of rare op words)
+    const uint32_t *opl;   // the window's block of rare op words
     const uint2 *bql;
     uint2 *runl;
-    uint32_t *q;   // [nslot + 128]: queued pieces (window index) from the front, X-run slots from the back
-                   // (with the extension: [min(2·nrare, nslot + 128)], the X-run slots of the rare pass
-                   // alone, a wave from either end)
+    uint32_t *q;   // [min(2·nrare, nslot + 128)]: the X-run slots of the rare pass, a wave from either end
 };
 __device__ __forceinline__ const uint32_t *phase16(const uint8_t *region, const void *src) {
     return (const uint32_t *)(region + ((uintptr_t)src & 15));
 }
-template <int NWP, bool EXT>
+template <int NWP>
 __device__ __forceinline__ WinLds win_lds(const DenseArgs &d, const Win &v, const XWin &xw, uint8_t *buf) {
     WinLds L;
-    const uint32_t *sop = EXT ? d.rop + xw.rop0 : d.ops + v.o0, *sbq = d.bq + 2 * (size_t)v.qw0;
-    if constexpr (!EXT) {
-        L.opl = phase16(buf, sop);
-        buf += dma16_bytes(v.nslot);
-    }
+    const uint32_t *sop = d.rop + xw.rop0, *sbq = d.bq + 2 * (size_t)v.qw0;
     L.bql = (const uint2 *)phase16(buf, sbq);
     buf += dma16_bytes(2 * v.nqw);
-    if constexpr (EXT) {
-        L.opl = phase16(buf, sop);
-        buf += dma16_bytes(xw.nrop);
-    }
+    L.opl = phase16(buf, sop);
+    buf += dma16_bytes(xw.nrop);
     L.runl = (uint2 *)buf;
-    L.q = (uint32_t *)(L.runl + v.nslot + run_pad<NWP, EXT>);
+    L.q = (uint32_t *)(L.runl + v.nslot + run_pad<NWP>);
     return L;
 }
 // issue the LDS-DMA of window v into buf, shared by the tile's waves (completion: every wave's
 // s_waitcnt vmcnt(0), then a barrier)
-template <int WPT, bool EXT>
+template <int WPT>
 __device__ __forceinline__ void win_issue(const DenseArgs &d, const Win &v, const XWin &xw, uint8_t *buf) {
-    if constexpr (!EXT) {
-        dma16<WPT>(buf, d.ops + v.o0, v.nslot, d.ops_end);
-        buf += dma16_bytes(v.nslot);
-    }
     dma16<WPT>(buf, d.bq + 2 * (size_t)v.qw0, 2 * v.nqw, d.bq_end);
-    if constexpr (EXT) {
-        // the rare pieces' op words, then the window's run records onto runl (its block starts
-        // 16-byte aligned: phase 0; the last 16 bytes of an odd block carry the host's zero pad
-        // record onto a pad record)
-        buf += dma16_bytes(2 * v.nqw);
-        dma16<WPT>(buf, d.rop + xw.rop0, xw.nrop, d.rop_end);
-        buf += dma16_bytes(xw.nrop);
-        dma16<WPT>(buf, d.drun + 2 * (size_t)xw.run0, 2 * v.nslot, d.drun_end);
-    }
+    // the rare pieces' op words, then the window's run records onto runl (its block starts
+    // 16-byte aligned: phase 0; the last 16 bytes of an odd block carry the host's zero pad
+    // record onto a pad record)
+    buf += dma16_bytes(2 * v.nqw);
+    dma16<WPT>(buf, d.rop + xw.rop0, xw.nrop, d.rop_end);
+    buf += dma16_bytes(xw.nrop);
+    dma16<WPT>(buf, d.drun + 2 * (size_t)xw.run0, 2 * v.nslot, d.drun_end);
 }
 
 // One tile of NWP words from its window in LDS, WPT waves (WT threads): a wave holds NWP / WPT
@@ -563,13 +535,12 @@ __device__ __forceinline__ void win_issue(const DenseArgs &d, const Win &v, cons
 // dcnt / ncnt / ccnt: zeroed byte counters; stl: the waves' partial tile statistics.
 constexpr int WPT = 2;   // waves per tile (they share the window)
 constexpr int WT = WGD * WPT;     // threads per tile
-constexpr int PFN = 2;   // piece records per thread loaded with the DMA (windows of ≤ PFN·WT pieces)
-// EXT: the walk from the windows' extension (xw; Pc[0] = this thread's rare record, Pc[1].y its
-// op words' offset in L.opl, Pc[1].x the thread's 'N' event), the run records already in runl.
-template <int NWP, bool EXT>
+// The walk from the windows' extension (xw), the run records already in runl.  Pc[0] = this
+// thread's rare record, Pc[1].y its op words' offset in L.opl, Pc[1].x the thread's 'N' event.
+template <int NWP>
 __device__ __forceinline__ void dense_tile(const DenseArgs &d, const Win &v, const XWin &xw, const WinLds &L, uint32_t *dcnt,
                                            uint32_t *ncnt, uint32_t *ccnt, const uint8_t *amb, uint32_t fill0,
-                                           const uint3 (&Pc)[PFN],
+                                           const uint3 (&Pc)[2],
                                            uint32_t cw0, uint32_t cw1, unsigned long long t_entry,
                                            uint32_t (*stl)[WPT][4], uint32_t tid, uint8_t *scratch) {
     constexpr int NWPW = NWP / WPT, G = WGD / NWPW, RPL = 8 / G;
@@ -579,8 +550,8 @@ __device__ __forceinline__ void dense_tile(const DenseArgs &d, const Win &v, con
     (void)t_entry;
 #endif
     PROF_MARK(1);   // phase 0: entry → window landed (scalar tile loads, DMA, piece records)
-    // (not const: with the extension they are formed again from the thread index after the count,
-    // so none of them holds a register through it — 96 VGPRs, five waves per SIMD)
+    // (not const: they are formed again from the thread index after the count, so none of them
+    // holds a register through it — 96 VGPRs, five waves per SIMD)
     uint32_t lane = tid & 63, wv = tid >> 6;
     uint32_t w = wv * NWPW + lane / G, g = lane % G;   // tile-relative word of this lane
     const uint32_t tile = v.tile, a = v.a, n = v.n, cb0 = v.cb0, npc = v.npc, o0 = v.o0, qw0 = v.qw0;
@@ -594,71 +565,27 @@ __device__ __forceinline__ void dense_tile(const DenseArgs &d, const Win &v, con
     const uint32_t *opl = L.opl, *bxl = d.bx + qw0;
     const uint2 *bql = L.bql;
     uint2 *runl = L.runl;
-    // this wave's queue: 64 entries per walk iteration (its pieces' share of the window).
-    // With the extension, the one queue of the tile holds the X runs of the rare pass's
-    // deletion reads alone, wave 0's from the front and wave 1's from the back.  Capacity rule:
-    // a deletion read adds at most 2 entries and owns 3 op slots, so the entries written are
-    // ≤ min(2·nrare, ⅔·nslot) ≤ qcap = min(2·nrare, nslot + 128), the queue's share of the
-    // window's LDS (S2C_DENSE_BYTES): the two ends never meet.
-    static_assert(!EXT || WPT == 2, "the X-run queue has two ends");
-    const uint32_t nitw = (npc + WT - 1) / WT, qcap = EXT ? min(2u * xw.nrare, v.nslot + 128u) : WGD * nitw;
-    uint32_t *queue = EXT ? L.q : L.q + wv * qcap;
-    const bool qback = !EXT || uni(wv) != 0u;   // this wave's X runs go in from the back
+    // The one queue of the tile holds the X runs of the rare pass's deletion reads, wave 0's
+    // from the front and wave 1's from the back.  Capacity rule: a deletion read adds at most 2
+    // entries and owns 3 op slots, so the entries written are ≤ min(2·nrare, ⅔·nslot) ≤ qcap =
+    // min(2·nrare, nslot + 128), the queue's share of the window's LDS (S2C_DENSE_LEAN_BYTES):
+    // the two ends never meet.
+    static_assert(WPT == 2, "the X-run queue has two ends");
+    const uint32_t qcap = min(2u * xw.nrare, v.nslot + 128u);
+    uint32_t *queue = L.q;
+    const bool qback = uni(wv) != 0u;   // this wave's X runs go in from the back
     auto xslot = [&](uint32_t i) { return qback ? qcap - 1u - i : i; };
 
-    // ---- walk: one lane per piece → run records (rec_enc) of the bases.  The one-token read
-    //      (S2C_PF_SIMPLE, 99 % of C5's pieces) takes the lean path below; every other piece
-    //      is compacted into the wave's queue and walked after the iterations
+    // ---- walk: the one-token reads (S2C_PF_SIMPLE, 99 % of C5's pieces) are the host's run
+    //      records; thread i takes rare piece i → run records (rec_enc) of its bases
     const int32_t T0 = (int32_t)(32 * W0), TL = (int32_t)(32 * nwords);   // the tile's words
     const bool mda = d.maxdel_active != 0;
-    // The wave's queue: the other pieces (their window index) from the front, the slots of
-    // runs waiting for the plane scan (X runs) from the back.  Capacity rule: a walk iteration
-    // adds at most one entry per lane (a piece is SIMPLE or not), so after the iterations
-    // nslow + nx ≤ 64·nitw = qcap.  The compacted pass reads a round's front entries before it
-    // writes: while front entries remain for later rounds the back may grow down to entry
-    // nslow (qcap − nslow − nx entries left), in the last round over the whole queue (qcap −
-    // nx); a round whose deletion reads' X runs (≤ 2 entries each) might not fit there sends
-    // those reads through the general walk, which scans their planes itself and queues nothing.
-    uint32_t nslow = 0, nx = 0;   // queue lengths (uniform)
-    const uint32_t nit = (EXT || ABL(4)) ? 0u : nitw;
-    // one M / = / X token and nothing else: seqout = SEQ[0 : take] (:64-69), take in the
-    // record's length field (s2c.h S2C_PF_SIMPLE): no op word read, no min
-    auto lean = [&](uint32_t k, const uint3 P) {
-        const DPiece D = dpc_dec(P.x, P.y);
-        const bool in = k < npc, simple = in && (D.fl & S2C_PF_SIMPLE) != 0u;
-        if (simple) {
-            runl[D.j] = rec_enc_b(D.rs, D.slen, D.q);
-            // at most two 'N' in SEQ (S2C_PF_XFEW: their SEQ offsets in px; 0xFFFF = none, never
-            // below take) straight into the 'N' counters
-            if (D.fl & S2C_PF_XFEW) {
-#pragma unroll
-                for (int u = 0; u < 2; u++) {
-                    const uint32_t off = (P.z >> (16 * u)) & 0xFFFFu;
-                    const int32_t r = (int32_t)(D.rs + off) - REC_BIAS;
-                    if (off < D.slen && r >= 0 && r < TL) cnt_add1(ncnt, (uint32_t)r);
-                }
-            }
-        }
-        // other non-ACGT chars in SEQ: the run's slot queued for the plane scan
-        const bool x1 = simple && (D.fl & (S2C_PF_X | S2C_PF_XFEW)) == S2C_PF_X;
-        const bool qd = in && !simple;
-        const uint64_t bs = __ballot(qd), bxm = __ballot(x1);
-        if (bs) {
-            if (qd) queue[nslow + mbcnt(bs)] = k;
-            nslow += (uint32_t)__popcll(bs);
-        }
-        if (bxm) {
-            if (x1) queue[xslot(nx + mbcnt(bxm))] = D.j;
-            nx += (uint32_t)__popcll(bxm);
-        }
-    };
-    // One piece that is not SIMPLE, from its compact record {c0, c1, pxv} (on: the lane holds
-    // one), shared by both paths; room: the X-run entries this round may add (the old path's
-    // capacity rule; the extension's queue always has room); rov: with the extension, the offset
-    // of the piece's op words in opl, the window's block of rare op words (else its op slot)
-    auto rare_piece = [&](bool on, uint32_t c0, uint32_t c1, uint32_t pxv, uint32_t room, uint32_t rov) {
+    uint32_t nx = 0;   // this wave's X runs queued (uniform)
+    // One rare piece from its record {c0, c1, pxv} (on: the lane holds one); ro: the offset of
+    // the piece's op words in opl, the window's block of rare op words
+    auto rare_piece = [&](bool on, uint32_t c0, uint32_t c1, uint32_t pxv, uint32_t ro) {
         const DPiece D = dpc_dec(c0, c1);
-        const uint32_t fl = D.fl, slen = D.slen, j = D.j, q = D.q, ro = EXT ? rov : j;
+        const uint32_t fl = D.fl, slen = D.slen, j = D.j, q = D.q;
         // bases, D / N / P, bases (the deletion reads) with no maxdel count to take (the rule is
         // off, or SEQ holds no '-'): two base runs (:64-72: k = take, then l1 '-', then
         // SEQ[l : l + min(l2, len(SEQ) − l)]) and the '-' run into the byte counters unless
@@ -674,16 +601,11 @@ __device__ __forceinline__ void dense_tile(const DenseArgs &d, const Win &v, con
             t2 = l < slen ? min(w2 >> 4, slen - l) : 0u;
         }
         // its non-ACGT chars: ≤ 2 'N' (S2C_PF_XFEW) from px below; else both base runs' slots go
-        // to the X-run queue if they fit (the capacity rule above)
+        // to the X-run queue (they fit: the capacity rule above)
         const bool xfew = (fl & S2C_PF_XFEW) != 0u;
         const bool xq = fdel && (fl & S2C_PF_X) != 0u && !xfew;
-        bool x2 = xq && t2 > 0u;
-        uint64_t bx1 = __ballot(xq), bx2 = __ballot(x2);
-        if (!EXT && bx1 && nx + (uint32_t)(__popcll(bx1) + __popcll(bx2)) > room) {
-            if (xq) fdel = false;
-            x2 = false;
-            bx1 = bx2 = 0;
-        }
+        const bool x2 = xq && t2 > 0u;
+        const uint64_t bx1 = __ballot(xq), bx2 = __ballot(x2);
         if (fdel) {
             runl[j] = rec_enc_b(D.rs, take, q);
             runl[j + 1] = make_uint2(0u, 0u);
@@ -723,66 +645,23 @@ __device__ __forceinline__ void dense_tile(const DenseArgs &d, const Win &v, con
                         });
         }
     };
-    if constexpr (EXT) {
-        // the 'N' events of the one-token reads (the host's list: tile-relative positions
-        // inside the tile's words), then thread i on rare piece i of the window's list
-        if (!ABL(4)) {
-            if (tid < xw.nnev) cnt_add1(ncnt, Pc[1].x);
-            for (uint32_t i = tid + WT; i < xw.nnev; i += WT) cnt_add1(ncnt, d.dnev[xw.nev0 + i]);
+    // the 'N' events of the one-token reads (the host's list: tile-relative positions inside
+    // the tile's words), then thread i on rare piece i of the window's list
+    if (!ABL(4)) {
+        if (tid < xw.nnev) cnt_add1(ncnt, Pc[1].x);
+        for (uint32_t i = tid + WT; i < xw.nnev; i += WT) cnt_add1(ncnt, d.dnev[xw.nev0 + i]);
+    }
+    PROF_MARK(2);
+    for (uint32_t base = 0; base < (ABL(16) ? 0u : xw.nrare); base += WT) {
+        const uint32_t i = base + tid;
+        const bool on = i < xw.nrare;
+        uint3 R = Pc[0];
+        uint32_t ro = Pc[1].y;
+        if (base) {   // (windows of more than WT rare pieces)
+            R = on ? ((const uint3 *)d.drare)[xw.rare0 + i] : make_uint3(0u, 0u, 0u);
+            ro = on ? d.roff[xw.rare0 + i] : 0u;
         }
-        PROF_MARK(2);
-        for (uint32_t base = 0; base < (ABL(16) ? 0u : xw.nrare); base += WT) {
-            const uint32_t i = base + tid;
-            const bool on = i < xw.nrare;
-            uint3 R = Pc[0];
-            uint32_t ro = Pc[1].y;
-            if (base) {   // (windows of more than WT rare pieces)
-                R = on ? ((const uint3 *)d.drare)[xw.rare0 + i] : make_uint3(0u, 0u, 0u);
-                ro = on ? d.roff[xw.rare0 + i] : 0u;
-            }
-            rare_piece(on, R.x, R.y, R.z, 0xFFFFFFFFu, ro);
-        }
-    } else {
-#pragma unroll
-        for (int u = 0; u < PFN; u++)
-            if ((uint32_t)u < nit) lean(tid + WT * u, Pc[u]);
-        for (uint32_t it = PFN; it < nit; it++) {   // (windows of more than WT·PFN pieces)
-            const uint32_t k = tid + WT * it;
-            lean(k, k < npc ? dpc_load(d, v.dpc0 + k) : make_uint3(0u, 0u, 0u));
-        }
-        // (the queued work below is this wave's own — its queue, its pieces' run records, atomic
-        // byte-counter adds — so its LDS writes completing is enough: the other wave's records are
-        // needed only by the count, after the barrier that ends the queued walks)
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        PROF_MARK(2);
-        // queued pieces, one per lane and round.  A piece's record comes from the lane that loaded
-        // it (ds_bpermute, all lanes on).
-        for (uint32_t base = 0; base < (ABL(16) ? 0u : nslow); base += WGD) {
-            const uint32_t i = base + lane;
-            const bool on = i < nslow;
-            const uint32_t k = on ? queue[i] : 0u, it = k / WT;
-            const int src = (int)(4 * (k % WGD));   // (k ≡ this wave's lane mod 64: WT is a multiple of 64)
-            uint32_t c0 = 0, c1 = 0, pxv = 0;
-#pragma unroll
-            for (int u = 0; u < PFN; u++) {
-                const uint32_t px = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)Pc[u].x);
-                const uint32_t py = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)Pc[u].y);
-                const uint32_t pz = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)Pc[u].z);
-                const bool me = it == (uint32_t)u;
-                c0 = me ? px : c0;
-                c1 = me ? py : c1;
-                pxv = me ? pz : pxv;
-            }
-            if (on && it >= (uint32_t)PFN) {   // (windows of more than WT·PFN pieces)
-                const uint3 R = dpc_load(d, v.dpc0 + k);
-                c0 = R.x;
-                c1 = R.y;
-                pxv = R.z;
-            }
-            // (front entries [base + 64, nslow) are still to be read: the back stays above nslow
-            // until the last round, which has read every front entry)
-            rare_piece(on, c0, c1, pxv, qcap - (base + WGD < nslow ? nslow : 0u), 0u);
-        }
+        rare_piece(on, R.x, R.y, R.z, ro);
     }
     lds_sync();   // every run record written
     PROF_MARK(3);
@@ -909,7 +788,7 @@ __device__ __forceinline__ void dense_tile(const DenseArgs &d, const Win &v, con
     // runs' parts in the lane's word — bases into the counters (planes from HBM), '-' runs and
     // the N / '-' chars of SEQ into the byte counters (the host keeps a dense tile's candidate
     // runs + long runs ≤ 255 per word)
-    if constexpr (EXT) {   // the lane's indices once more (opaque: not kept from before the count)
+    {   // the lane's indices once more (opaque: not kept from before the count)
         uint32_t t = tid;
         asm volatile("" : "+v"(t));
         lane = t & 63, wv = t >> 6;
@@ -964,13 +843,12 @@ __device__ __forceinline__ void dense_tile(const DenseArgs &d, const Win &v, con
         }
     }
     PROF_MARK(5);
-    // queued single-token runs of reads with N / '-' in SEQ (never dropped: maxdel is off; 0.08
-    // per C5 wave: read here, where their registers are not live through the count)
-    if constexpr (EXT) {   // (the one-token reads' X runs: the host's list of their slots)
-        for (uint32_t i = tid; i < (ABL(32) ? 0u : xw.nxs); i += WT) {
-            const Rec rc = rec_dec(runl[d.dxs[xw.xs0 + i]]);
-            x_events(bxl, bql, rc.q, rc.l, rc.r0, TL, false, dcnt, ncnt, ccnt);
-        }
+    // runs of reads with N / '-' in SEQ (never dropped: maxdel is off; 0.08 per C5 wave: read
+    // here, where their registers are not live through the count): the one-token reads' X runs
+    // from the host's list of their slots, then the deletion reads' from this wave's queue
+    for (uint32_t i = tid; i < (ABL(32) ? 0u : xw.nxs); i += WT) {
+        const Rec rc = rec_dec(runl[d.dxs[xw.xs0 + i]]);
+        x_events(bxl, bql, rc.q, rc.l, rc.r0, TL, false, dcnt, ncnt, ccnt);
     }
     for (uint32_t i = lane; i < (ABL(32) ? 0u : nx); i += WGD) {
         const Rec rc = rec_dec(runl[queue[xslot(i)]]);
@@ -1005,9 +883,9 @@ __device__ __forceinline__ void dense_tile(const DenseArgs &d, const Win &v, con
         const uint32_t part = PARTS == 2 ? (g >= 4 ? 1u : 0u) : 0u;
         const uint32_t cb = PARTS == 2 ? min(g, 7u - g) : (g % (uint32_t)SRC) * (uint32_t)CPL;
         const uint32_t src0 = wl * G + part * SRC;
-        // this wave's scratch (with the extension: sized for the launch's plane pairs, which a
-        // lane's count here never exceeds — the host's S2C_DENSE_PAIRS over the same counts)
-        uint2 *xp = (uint2 *)(scratch + wv * (EXT ? d.xch_wave : XCH_WAVE_BYTES));
+        // this wave's scratch (sized for the launch's plane pairs, which a lane's count here
+        // never exceeds — the host's S2C_DENSE_PAIRS over the same counts)
+        uint2 *xp = (uint2 *)(scratch + wv * d.xch_wave);
         uint32_t *vp = (uint32_t *)xp;   // the rows (aliases the planes: read before, in wave order)
         // a lane's count ≤ its record slots + long rounds: planes 0 .. 2·NCH − 1 carry it (s2c.h
         // S2C_DENSE_SLOTS / S2C_DENSE_PAIRS: the rule the host sizes the launch's exchange by)
@@ -1278,7 +1156,7 @@ __device__ __forceinline__ void dense_tile(const DenseArgs &d, const Win &v, con
         atomicAdd(&g_prof[9], (unsigned long long)ngrp);
         atomicAdd(&g_prof[10], (unsigned long long)npc);
         atomicAdd(&g_prof[11], (unsigned long long)(v.nslot + 3 * v.nqw));
-        atomicAdd(&g_prof[12], (unsigned long long)(EXT ? xw.nrare : nslow));
+        atomicAdd(&g_prof[12], (unsigned long long)xw.nrare);
         atomicAdd(&g_prof[13], (unsigned long long)nx);
     }
 #endif
@@ -1287,11 +1165,11 @@ __device__ __forceinline__ void dense_tile(const DenseArgs &d, const Win &v, con
 // One workgroup of WPT waves per tile (block b → item, XCD-major: the blocks of one XCD, b ≡ x mod 8, take a
 // contiguous range of items, so neighbouring windows meet in that XCD's L2).  Everything the
 // tile needs arrives by one LDS-DMA round trip after the scalar loads of its tile record.
-// (with the extension: at most 96 VGPRs, so five waves fit a SIMD — nine tiles per CU where the
-// batch's windows and exchange leave the LDS for them; scripts/check_spills.py holds the 96)
-template <int NWP, bool EXT>
-__global__ __launch_bounds__(WT, EXT ? 5 : 4) void k_tile_dense(const DenseArgs d) {
-    extern __shared__ uint4 arena[];   // the window (S2C_DENSE_BYTES layout)
+// (at most 96 VGPRs, so five waves fit a SIMD — nine tiles per CU where the batch's windows and
+// exchange leave the LDS for them; scripts/check_spills.py holds the 96)
+template <int NWP>
+__global__ __launch_bounds__(WT, 5) void k_tile_dense(const DenseArgs d) {
+    extern __shared__ uint4 arena[];   // the window (S2C_DENSE_LEAN_BYTES layout)
     // one byte per position (row layout): '-' (D/N/P runs, '-' of SEQ unless maxdel drops
     // the read's), 'N' of SEQ, '-' of SEQ (all: the planes count them as C, and 'N' as A)
     __shared__ __attribute__((aligned(16))) uint32_t dcnt[8 * NWP], ncnt[8 * NWP], ccnt[8 * NWP];
@@ -1313,30 +1191,22 @@ __global__ __launch_bounds__(WT, EXT ? 5 : 4) void k_tile_dense(const DenseArgs 
     const uint32_t x = b & 7u, per = d.n_items >> 3, rem = d.n_items & 7u;
     const uint32_t item = x * per + min(x, rem) + (b >> 3);
     XWin xw;
-    const Win v = win_of<EXT>(d, item, xw);
+    const Win v = win_of(d, item, xw);
     uint8_t *const buf = (uint8_t *)arena;
-    win_issue<WPT, EXT>(d, v, xw, buf);
-    const WinLds wl = win_lds<NWP, EXT>(d, v, xw, buf);
-    if (tid < run_pad<NWP, EXT>) wl.runl[v.nslot + tid] = make_uint2(0u, 0u);   // (the DMA does not write there)
-    // with the DMA: the thread's piece records and its word's run-slot range
+    win_issue<WPT>(d, v, xw, buf);
+    const WinLds wl = win_lds<NWP>(d, v, xw, buf);
+    if (tid < run_pad<NWP>) wl.runl[v.nslot + tid] = make_uint2(0u, 0u);   // (the DMA does not write there)
+    // with the DMA: the thread's rare record (s2c.h S2C_DPC_WORDS), its 'N' event and its word's
+    // run-slot range (dense_tile loads the rest in its loops)
     constexpr int G = WGD / (NWP / WPT);
-    uint3 Pc[PFN];   // (compact records: s2c.h S2C_DPC_WORDS)
+    uint3 Pc[2];   // (kept as two records set to zero in a loop: named scalars here move two VGPRs)
 #pragma unroll
-    for (int i = 0; i < PFN; i++) {
-        const uint32_t k = tid + WT * i;
-        Pc[i] = make_uint3(0u, 0u, 0u);
-        if constexpr (!EXT) {
-            if (k < v.npc) Pc[i] = dpc_load(d, v.dpc0 + k);
-        }
+    for (int i = 0; i < 2; i++) Pc[i] = make_uint3(0u, 0u, 0u);
+    if (tid < xw.nrare) {
+        Pc[0] = ((const uint3 *)d.drare)[xw.rare0 + tid];
+        Pc[1].y = d.roff[xw.rare0 + tid];   // (its op words' offset in the window's block)
     }
-    if constexpr (EXT) {   // (dense_tile: the thread's rare record and its 'N' event; the rest in its loops)
-        static_assert(PFN >= 2, "Pc[1] holds the 'N' event");
-        if (tid < xw.nrare) {
-            Pc[0] = ((const uint3 *)d.drare)[xw.rare0 + tid];
-            Pc[1].y = d.roff[xw.rare0 + tid];   // (its op words' offset in the window's block)
-        }
-        if (tid < xw.nnev) Pc[1].x = d.dnev[xw.nev0 + tid];
-    }
+    if (tid < xw.nnev) Pc[1].x = d.dnev[xw.nev0 + tid];
     const uint32_t w = (tid >> 6) * (NWP / WPT) + (tid & 63) / G, W = v.W0 + w, K = d.kwin;
     uint32_t cw0 = 0, cw1 = 0;
     if (w < v.nwords) {   // (window-relative after the wait below: no early wait on the DMA)
@@ -1364,23 +1234,21 @@ __global__ __launch_bounds__(WT, EXT ? 5 : 4) void k_tile_dense(const DenseArgs 
     cw0 -= v.o0;
     cw1 -= v.o0;
     lds_sync();
-    dense_tile<NWP, EXT>(d, v, xw, wl, dcnt, ncnt, ccnt, amb, fill0, Pc, cw0, cw1, t_entry, stl, threadIdx.x, buf);
+    dense_tile<NWP>(d, v, xw, wl, dcnt, ncnt, ccnt, amb, fill0, Pc, cw0, cw1, t_entry, stl, threadIdx.x, buf);
 }
 
 
-// lean: the extension's launch — dynamic LDS = the largest lean window or the exchange of its
-// plane pairs (s2c.h s2c_dense_lean); else the window with its op words, the exchange of all 8 planes
+// dynamic LDS = the batch's largest window (lds) or the exchange of its plane pairs (s2c.h s2c_dense_lean)
 template <int NWP>
-int launch(DenseArgs a, const s2c_dense_lean *lean, int64_t lds, int64_t n, hipStream_t s) {
+int launch(DenseArgs a, const s2c_dense_lean &lean, int64_t lds, int64_t n, hipStream_t s) {
     static_assert(S2C_DENSE_XCH_BYTES(XCH_NCH_MAX, NWP) == WPT * XCH_WAVE_BYTES && XCH_WAVE_BYTES / XCH_NCH_MAX == 2080 &&
                       XCH_VROW * 4 * (NWP / WPT) == 80 * NWP, "s2c.h S2C_DENSE_XCH_BYTES");
-    a.xch_wave = (uint32_t)(lean ? S2C_DENSE_XCH_BYTES(lean->pairs, NWP) / WPT : XCH_WAVE_BYTES);
-    a.buf_bytes = (uint32_t)std::max<int64_t>(lds + (WPT > 2 ? 256 * WPT : 0), (int64_t)WPT * a.xch_wave);
+    a.xch_wave = (uint32_t)(S2C_DENSE_XCH_BYTES(lean.pairs, NWP) / WPT);
+    a.buf_bytes = (uint32_t)std::max<int64_t>(lds, (int64_t)WPT * a.xch_wave);
 #ifdef S2C_DENSE_LDS_ADD   // (a `make variant` build: the LDS share at which one tile fewer resides per CU, found by running)
     a.buf_bytes += S2C_DENSE_LDS_ADD;
 #endif
-    if (lean) k_tile_dense<NWP, true><<<(unsigned)n, WT, a.buf_bytes, s>>>(a);
-    else k_tile_dense<NWP, false><<<(unsigned)n, WT, a.buf_bytes, s>>>(a);
+    k_tile_dense<NWP><<<(unsigned)n, WT, a.buf_bytes, s>>>(a);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? S2C_OK : s2c_set_error(S2C_ERR_HIP, std::string("k_tile_dense: ") + hipGetErrorString(e));
 }
@@ -1402,22 +1270,19 @@ extern "C" int s2c_prof_dense(unsigned long long *out, int reset) {
 }
 #endif
 
-int s2c_launch_dense(const s2c_dev *dv, const s2c_dense_ext *ext, const s2c_dense_lean *lean, hipStream_t st) {
+// (the caller, s2c_pileup_lean, has checked dv, ext and lean, and that the batch has dense tiles
+// and a one-char fill)
+int s2c_launch_dense(const s2c_dev *dv, const s2c_dense_ext &ext, const s2c_dense_lean &lean, hipStream_t st) {
     using namespace s2c;
     if (dv->n_dense <= 0) return S2C_OK;
     if (dv->fill_len != 1) return s2c_set_error(S2C_ERR_ARG, "dense tiles need a one-char fill");
     if (dv->n_dense >= ((int64_t)1 << 31)) return s2c_set_error(S2C_ERR_LIMIT, "too many dense tiles");
-    DenseArgs a;
-    // (with the windows' extension and its lean part — checked by the caller, s2c_pileup_lean: both
-    // or neither — dpc is not read)
-    if ((!ext && !dv->dpc) || !dv->dwin) return s2c_set_error(S2C_ERR_ARG, "dense tiles need dwin and dpc (ABI 12)");
-    if ((ext != nullptr) != (lean != nullptr)) return s2c_set_error(S2C_ERR_ARG, "s2c_dense_ext and s2c_dense_lean go together");
-    a.rop = lean ? lean->rop : nullptr; a.roff = lean ? lean->roff : nullptr; a.drow = lean ? lean->row : nullptr;
-    a.rop_end = lean ? lean->rop + lean->n_rop : nullptr;
-    a.drun = ext ? ext->drun : nullptr; a.dnev = ext ? ext->dnev : nullptr; a.dxs = ext ? ext->dxs : nullptr;
-    a.drare = ext ? ext->drare : nullptr; a.dext = ext ? ext->dext : nullptr;
-    a.drun_end = ext ? ext->drun + 2 * ext->n_drun : nullptr;
-    a.rs = dv->rs; a.lp = dv->lp; a.pc = dv->pc; a.dwin = dv->dwin; a.dpc = dv->dpc; a.ops = dv->ops; a.bq = dv->bq; a.bx = dv->bx; a.tiles = dv->tiles; a.items = dv->dense;
+    DenseArgs a = {};
+    a.rop = lean.rop; a.roff = lean.roff; a.drow = lean.row;
+    a.rop_end = lean.rop + lean.n_rop;
+    a.drun = ext.drun; a.dnev = ext.dnev; a.dxs = ext.dxs; a.drare = ext.drare; a.dext = ext.dext;
+    a.drun_end = ext.drun + 2 * ext.n_drun;
+    a.rs = dv->rs; a.lp = dv->lp; a.pc = dv->pc; a.dwin = dv->dwin; a.ops = dv->ops; a.bq = dv->bq; a.bx = dv->bx; a.tiles = dv->tiles; a.items = dv->dense;
     a.thresholds = dv->thresholds; a.tile_stats = dv->tile_stats; a.blk_len = dv->blk_len; a.out = dv->out;
     a.padded_len = (uint32_t)dv->padded_len; a.n_cols = (uint32_t)dv->n_cols; a.n_tiles = (uint32_t)dv->n_tiles;
     a.kwin = (uint32_t)dv->kwin; a.fill_nondash = (uint32_t)dv->fill_nondash;
@@ -1425,20 +1290,18 @@ int s2c_launch_dense(const s2c_dev *dv, const s2c_dense_ext *ext, const s2c_dens
     a.maxdel = dv->maxdel < 0 ? 0u : (uint32_t)dv->maxdel;
     a.n_items = (uint32_t)dv->n_dense;
     a.word_lo = (uint32_t)dv->word_lo;
-    a.ops_end = dv->ops + dv->n_ops;
     a.bq_end = dv->bq + 2 * dv->n_qwords;
     a.n_thr = dv->n_thr; a.min_depth = dv->min_depth;
     a.fill = dv->fill;
     const int64_t n = dv->n_dense;
-    // LDS: the largest window of the batch (S2C_DENSE_BYTES, host plan; with the extension
-    // S2C_DENSE_LEAN_BYTES, s2c_dense_lean.lds — never more)
-    const int64_t lds = lean ? lean->lds : dv->dense_lds;
+    // LDS: the largest window of the batch (S2C_DENSE_LEAN_BYTES, s2c_dense_lean.lds — never
+    // more than the host plan's S2C_DENSE_BYTES bound, dense_lds)
+    const int64_t lds = lean.lds;
     if (dv->dense_lds <= 0 || dv->dense_lds > S2C_DENSE_LDS || (dv->dense_lds & 15))
         return s2c_set_error(S2C_ERR_ARG, "dense_lds outside (0, S2C_DENSE_LDS] or not 16-byte aligned");
     if (lds <= 0 || lds > dv->dense_lds || (lds & 15))
         return s2c_set_error(S2C_ERR_ARG, "s2c_dense_lean: lds outside (0, s2c_dev.dense_lds] or not 16-byte aligned");
     // (the window's LDS doubles as the counters' exchange after the count: at least WPT waves' share)
-    // (WPT > 2: the waves' queues may take up to 64·WPT entries past S2C_DENSE_BYTES' share)
     static_assert(WPT * XCH_WAVE_BYTES == S2C_DENSE_MIN_LDS, "s2c.h S2C_DENSE_MIN_LDS (the host's occupancy plan)");
     if constexpr (WPT <= 2) {   // (≥ 8 words per wave)
         if (dv->tile_max <= 512) return launch<16>(a, lean, lds, n, st);

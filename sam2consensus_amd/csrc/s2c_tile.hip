@@ -27,7 +27,7 @@
 #include "s2c_common.h"
 
 int s2c_launch_reads(const s2c_dev *d, hipStream_t s, bool all, bool run);
-int s2c_launch_dense(const s2c_dev *d, const s2c_dense_ext *ext, const s2c_dense_lean *lean, hipStream_t s);
+int s2c_launch_dense(const s2c_dev *d, const s2c_dense_ext &ext, const s2c_dense_lean &lean, hipStream_t s);
 
 #ifdef S2C_PROF
 // phase clocks of k_tile (diagnostic build `make prof`, scripts/prof_tile.py): Σ over sampled
@@ -2013,6 +2013,7 @@ TileArgs tile_args(const s2c_dev &d) {
 template <int NWP>
 int launch_tile(const TileArgs &a, const uint32_t *items, int64_t n, hipStream_t s) {
     if (n <= 0) return S2C_OK;
+    if (n >= ((int64_t)1 << 31)) return s2c_set_error(S2C_ERR_LIMIT, "too many work items");   // (as s2c_launch_dense: a grid's blocks)
     if (a.walk_queue) k_tile<NWP, true><<<(unsigned)n, WG, 0, s>>>(a, items);
     else k_tile<NWP, false><<<(unsigned)n, WG, 0, s>>>(a, items);
     return hip_check(hipGetLastError(), "k_tile");
@@ -2100,7 +2101,7 @@ extern "C" int s2c_reads(const s2c_dev *d, void *stream) {
     return s2c_launch_reads(d, (hipStream_t)stream, false, true);
 }
 
-// the dense windows' extension of s2c_pileup_ext / s2c_run_ext (s2c.h), after check_dev
+// the dense windows' extension of s2c_pileup_lean / s2c_run_lean (s2c.h), after check_dev
 static int check_ext(const s2c_dev *d, const s2c_dense_ext *x) {
     if (!x) return S2C_OK;
     const struct { const uint32_t *p; int64_t n; const char *name; } a[5] = {
@@ -2136,6 +2137,15 @@ static int check_lean(const s2c_dev *d, const s2c_dense_ext *x, const s2c_dense_
     return S2C_OK;
 }
 
+// k_tile_dense (dense tiles, a one-char fill) walks from the windows' extension alone, after
+// check_lean (both parts or neither): refused before anything is launched
+static int check_dense_walk(const s2c_dev *d, const s2c_dense_ext *x) {
+    if (d->n_dense > 0 && d->fill_len == 1 && !x)
+        return s2c_set_error(S2C_ERR_ARG, "dense tiles with a one-char fill run from their windows' extension: "
+                                          "s2c_run_lean / s2c_pileup_lean with s2c_dense_ext and s2c_dense_lean");
+    return S2C_OK;
+}
+
 extern "C" int s2c_pileup_lean(const s2c_dev *d, const s2c_dense_ext *ext, const s2c_dense_lean *lean, void *stream) {
     int rc = check_dev(d);
     if (rc) return rc;
@@ -2144,18 +2154,17 @@ extern "C" int s2c_pileup_lean(const s2c_dev *d, const s2c_dense_ext *ext, const
     if (d->n_dense > 0 && d->fill_len != 1 && !d->layers_dense)
         return s2c_set_error(S2C_ERR_ARG, "a fill of length != 1 runs the dense tiles through k_tile: their layered "
                                           "windows are needed (s2c_batch_layers_mode(b, 1))");
-    if ((rc = check_ext(d, ext)) || (rc = check_lean(d, ext, lean))) return rc;
+    if ((rc = check_ext(d, ext)) || (rc = check_lean(d, ext, lean)) || (rc = check_dense_walk(d, ext))) return rc;
     hipStream_t s = (hipStream_t)stream;
     const TileArgs a = tile_args(*d);
     // (the deep tiles' HBM counts are zero: before the first run by the caller, after every
     // run by s2c_consensus — s2c_dev.counts)
     if (d->n_dense > 0) {
-        rc = d->fill_len == 1 ? s2c_launch_dense(d, ext, lean, s) : launch_tiles(a, d->tile_max, d->dense, d->n_dense, s);
+        rc = d->fill_len == 1 ? s2c_launch_dense(d, *ext, *lean, s) : launch_tiles(a, d->tile_max, d->dense, d->n_dense, s);
         if (rc) return rc;
     }
     return launch_tiles(a, d->tile_max, d->items, d->n_items, s);
 }
-extern "C" int s2c_pileup_ext(const s2c_dev *d, const s2c_dense_ext *ext, void *stream) { return s2c_pileup_lean(d, ext, nullptr, stream); }
 extern "C" int s2c_pileup(const s2c_dev *d, void *stream) { return s2c_pileup_lean(d, nullptr, nullptr, stream); }
 
 extern "C" int s2c_consensus(const s2c_dev *d, void *stream) {
@@ -2170,12 +2179,12 @@ extern "C" int s2c_consensus(const s2c_dev *d, void *stream) {
 
 extern "C" int s2c_run_lean(const s2c_dev *d, const s2c_dense_ext *ext, const s2c_dense_lean *lean, void *stream) {
     int rc;
-    if ((rc = check_dev(d)) || (rc = check_ext(d, ext)) || (rc = check_lean(d, ext, lean))) return rc;   // (a bad extension: before s2c_reads launches)
+    // (a bad or missing extension: before s2c_reads launches)
+    if ((rc = check_dev(d)) || (rc = check_ext(d, ext)) || (rc = check_lean(d, ext, lean)) || (rc = check_dense_walk(d, ext))) return rc;
     if ((rc = s2c_reads(d, stream))) return rc;
     if ((rc = s2c_pileup_lean(d, ext, lean, stream))) return rc;
     return s2c_consensus(d, stream);
 }
-extern "C" int s2c_run_ext(const s2c_dev *d, const s2c_dense_ext *ext, void *stream) { return s2c_run_lean(d, ext, nullptr, stream); }
 extern "C" int s2c_run(const s2c_dev *d, void *stream) { return s2c_run_lean(d, nullptr, nullptr, stream); }
 
 extern "C" int s2c_pileup_counts(const s2c_dev *d, void *stream) {

@@ -8,8 +8,9 @@ from . import _lib as L
 # the packed batch's device arrays, in upload order (s2c_dev's pointer fields)
 ARRAYS = ("pc", "ops", "bq", "bx", "rs", "tiles", "items", "dense", "deep", "lp", "wtile", "rlist", "ps",
           "lly", "lpc", "lops", "lbq", "lbx", "px", "dwin", "lpx", "dpc")
-# the dense windows' extension (s2c_dense_ext), uploaded in place of dpc: with it k_tile_dense
-# does not read the compact records (UPLOAD: what a run through the _ext entries uploads)
+# the dense windows' extension (s2c_dense_ext), what k_tile_dense walks from.  dpc, the host's
+# compact records it is written from, is read by no kernel and is not uploaded (UPLOAD: what a
+# run uploads; s2c_dev.dpc stays NULL)
 EXT_ARRAYS = ("drun", "dnev", "dxs", "drare", "dext")
 # ... and its lean part (s2c_dense_lean: the rare pieces' op words, their offsets, the windows' rows)
 LEAN_ARRAYS = ("rop", "roff", "drow")
@@ -24,7 +25,7 @@ def fill_dev(info, arrays, bufs, n_thr, min_depth, fill, maxdel_active, maxdel, 
     i = info
     d = L.Dev()
     for name in ARRAYS:
-        setattr(d, name, arrays.get(name))   # (dpc: None, i.e. NULL, when the extension replaces it)
+        setattr(d, name, arrays.get(name))   # (dpc: None, i.e. NULL — no longer read)
     d.n_pieces, d.n_ops, d.n_qwords, d.n_tiles = i.n_pieces, i.n_ops, i.n_qwords, i.n_tiles
     d.n_items, d.n_dense, d.n_deep = i.n_items, i.n_dense, i.n_deep
     d.padded_len, d.chunk, d.kwin, d.tile_max = i.padded_len, i.chunk, i.kwin, i.tile_max

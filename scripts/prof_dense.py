@@ -25,7 +25,7 @@ f.argtypes = [C.POINTER(C.c_ulonglong), C.c_int]
 abl = _lib.lib.s2c_prof_ablate
 abl.argtypes = [C.c_uint32]
 buf = (C.c_ulonglong * 16)()
-names = ["prologue (tile loads, DMA, wait)", "walk fast", "walk slow", "walk N/-", "count", "fixup+transpose", "vote+store"]
+names = ["prologue (tile loads, DMA, wait)", "walk 'N' events", "walk rare pieces", "walk N/-", "count", "fixup+transpose", "vote+store"]
 bits_list = [int(b) for b in sys.argv[2].split(",")] if len(sys.argv) > 2 else [0]
 for bits in bits_list:
     abl(bits)
@@ -42,9 +42,9 @@ for bits in bits_list:
     f(buf, 0)
     waves = max(buf[8], 1)
     tot = sum(buf[i] for i in range(len(names)))
-    print("ablate %d (1 events, 2 count, 4 walk, 8 vote, 16 queued walk, 32 N/- events): step %.3f ms" % (bits, ev0.elapsed_time(ev1) / N))
+    print("ablate %d (1 events, 2 count, 4 walk, 8 vote, 16 rare pieces' walk, 32 N/- events): step %.3f ms" % (bits, ev0.elapsed_time(ev1) / N))
     for i, nm in enumerate(names):
         print("  %-18s %9.0f cyc/wave  %5.1f%%" % (nm, buf[i] / waves, 100.0 * buf[i] / max(tot, 1)))
-    print("  groups/wave %.1f pieces/wave %.1f staged dwords/wave %.0f slow/wave %.2f xq/wave %.2f" % (
+    print("  groups/wave %.1f pieces/wave %.1f staged dwords/wave %.0f rare/wave %.2f xq/wave %.2f" % (
         buf[9] / waves, buf[10] / waves, buf[11] / waves, buf[12] / waves, buf[13] / waves), flush=True)
 abl(0)

@@ -15,7 +15,7 @@ import os
 import sys
 from collections import defaultdict
 
-NAMES = {1: "events", 2: "count", 4: "walk (fast + queue)", 8: "vote + store", 16: "queued walk", 32: "N / '-' events",
+NAMES = {1: "events", 2: "count", 4: "walk ('N' events)", 8: "vote + store", 16: "rare pieces' walk", 32: "N / '-' events",
          64: "slow votes"}
 
 

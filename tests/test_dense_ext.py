@@ -1,13 +1,13 @@
 """The dense windows' extension (s2c.h s2c_dense_ext): the run records, 'N' events, X-run slots
 and rare pieces' records the host writes beside the compact piece records, and k_tile_dense's
-walk from them (s2c_run_ext / s2c_pileup_ext).
+walk from them (s2c_run_lean / s2c_pileup_lean).
 
 Without a GPU: the five arrays equal a numpy model built from pc, px, dwin and tiles alone — on
 every case of test_dense_walk, on one more case of many 'N' events, on a C5-like batch and on
 its shards; the X-run queue of the rare pass stays inside its capacity; the C-ABI refuses a
-malformed extension before any launch.  On the GPU: a run with the extension and a run without
-it (the compact records' walk) give the same statistics, offsets and body bytes, both equal to
-the batch model and the oracle's FASTA files, each twice on one workspace."""
+malformed extension before any launch.  On the GPU: the walk gives the batch model's statistics,
+offsets and body bytes and the oracle's FASTA files, twice on one workspace; through a tile range
+it gives the same bytes and the whole batch's statistics of those tiles."""
 import ctypes as C
 import functools
 import random
@@ -131,9 +131,9 @@ def test_extension_equals_numpy_model(name):
     if name == "many_dels":
         assert (hb.dext[:, 7] > WT).any()        # more rare pieces than threads
     if name == "big_window":
-        # (past the compact-record walk's register-held records; the extension's own are covered by
-        # n_events and many_dels)
-        assert (hb.dwin[:, 7].astype(np.int64) - hb.dwin[:, 6] > WT * tdw.PFN).any() and hb.dext[:, 3].any() and hb.dext[:, 7].any()
+        # (windows of more than 256 pieces; more 'N' events and more rare pieces than threads are
+        # n_events' and many_dels')
+        assert (hb.dwin[:, 7].astype(np.int64) - hb.dwin[:, 6] > tdw.BIG_WINDOW).any() and hb.dext[:, 3].any() and hb.dext[:, 7].any()
 
 
 def test_extension_equals_numpy_model_c5_and_shards():
@@ -182,12 +182,21 @@ def _ext_of(hb):
     return x
 
 
-def test_run_ext_refuses_a_malformed_extension_before_launch():
-    """S2C_ERR_ARG over host pointers (never dereferenced: the calls return before any launch)."""
+def _lean_of(hb):
+    y = L.DenseLean()
+    L.check(L.lib.s2c_batch_dense_lean_get(hb._b, C.byref(y)))
+    return y
+
+
+def test_run_lean_refuses_a_malformed_extension_before_launch():
+    """S2C_ERR_ARG over host pointers (never dereferenced: the calls return before any launch),
+    with a valid lean part beside the extension: the extension is checked first."""
     _, _, hb, _, _ = _case("dels_maxdel_on")
     hb.ensure_layers()
     d, keep = _host_dev(hb)
-    for f in (L.lib.s2c_run_ext, L.lib.s2c_pileup_ext):
+    y = _lean_of(hb)
+    for g in (L.lib.s2c_run_lean, L.lib.s2c_pileup_lean):
+        f = lambda dv, x, stream, g=g: g(dv, x, C.byref(y), stream)  # noqa: E731
         for name in ("drun", "dnev", "dxs", "drare", "dext"):
             x = _ext_of(hb)
             setattr(x, "n_" + name, max(getattr(x, "n_" + name), 1))
@@ -211,58 +220,59 @@ def test_run_ext_refuses_a_malformed_extension_before_launch():
         assert "no thresholds" in L.last_error()
 
 
-def _both_paths(hb, opt, tile_range=None):
-    """(workspace, run with the extension, run without it): the second through s2c_run over the
-    same buffers with the compact records uploaded beside the batch."""
-    import torch
+def _workspace(hb, opt, tile_range=None):
+    """The case's workspace (its run is s2c_run_lean with the batch's extension)."""
     from sam2consensus_amd import engine
     fill = opt.fill.encode()
     db = engine.DeviceBatch(hb, dense_layers=engine.needs_dense_layers(fill, False))
-    ws = engine.Workspace(db, opt.thresholds, opt.min_depth, fill, False, tile_range=tile_range)
-    dpc = engine._up(np.ascontiguousarray(hb.dpc).reshape(-1), db.device)
-    old = L.Dev.from_buffer_copy(ws.dev)
-    old.dpc = dpc.data_ptr()
-
-    def run_old():
-        L.check(L.lib.s2c_run(C.byref(old), ws.stream_handle()))
-        torch.cuda.current_stream(db.device).synchronize()
-    return ws, ws.run, run_old, dpc
+    return engine.Workspace(db, opt.thresholds, opt.min_depth, fill, False, tile_range=tile_range)
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", list(CASES))
-def test_extension_walk_equals_compact_record_walk_model_and_oracle(name):
+def test_extension_walk_equals_model_and_oracle(name):
     _, opt, hb, want, ref = _case(name)
-    ws, run_new, run_old, keep = _both_paths(hb, opt)
-    for run in (run_new, run_old):
-        for _ in range(2):
-            ws.out.zero_(), ws.tile_stats.zero_(), ws.blk_len.zero_()   # (nothing of the other path's run is left)
-            run()
-            st, offs, out = ws.fetch()
-            assert (st == want[0]).all()
-            assert (offs == want[1]).all()
-            assert out == want[2]
-        assert tdw._files(hb, opt, st, offs, out) == ref["files"]
+    ws = _workspace(hb, opt)
+    for _ in range(2):
+        ws.out.zero_(), ws.tile_stats.zero_(), ws.blk_len.zero_()   # (nothing of the earlier run is left)
+        ws.run()
+        st, offs, out = ws.fetch()
+        assert (st == want[0]).all()
+        assert (offs == want[1]).all()
+        assert out == want[2]
+    assert tdw._files(hb, opt, st, offs, out) == ref["files"]
+
+
+def _tile_stats(ws, T, nb):
+    """The device's per-tile statistics of a finished run, [T][n_tiles][4] u64."""
+    import torch
+    return ws.tile_stats[: T * nb * 32].view(torch.int64).cpu().numpy().view(np.uint64).reshape(T, nb, 4)
 
 
 @pytest.mark.gpu
 def test_extension_walk_through_a_tile_range():
-    """A workspace over tiles [1, n): dext filtered like dwin; both paths give the model's bytes."""
+    """A workspace over tiles [1, n): dext filtered like dwin; it gives the model's bytes, and its
+    per-tile statistics of tiles [1, n) are the rows of a whole-batch workspace's run."""
     _, opt, hb, want, _ = _case("big_window")
     nb, T = int(hb.info.n_tiles), len(opt.thresholds)
     assert nb > 2 and hb.info.n_dense == nb
     t0, t1 = 1, nb
-    ws, run_new, run_old, keep = _both_paths(hb, opt, tile_range=(t0, t1))
+    ws = _workspace(hb, opt, tile_range=(t0, t1))
     assert ws.ext.n_dext == ws.dev.n_dense == t1 - t0
     wo = want[1].astype(np.int64)
     body = b"".join(bytes(want[2][wo[t * nb + t0]:wo[t * nb + t1]]) for t in range(T))
     lens = np.concatenate([np.diff(wo)[t * nb + t0:t * nb + t1] for t in range(T)])
-    got = []
-    for run in (run_new, run_old):
-        ws.out.zero_(), ws.tile_stats.zero_(), ws.blk_len.zero_()
-        run()
-        st, offs, out = ws.fetch()
-        assert (np.diff(offs.astype(np.int64)) == lens).all()
-        assert bytes(out) == body
-        got.append(st)
-    assert (got[0] == got[1]).all()
+    ws.out.zero_(), ws.tile_stats.zero_(), ws.blk_len.zero_()
+    ws.run()
+    st, offs, out = ws.fetch()
+    assert (np.diff(offs.astype(np.int64)) == lens).all()
+    assert bytes(out) == body
+    part = _tile_stats(ws, T, nb)
+    whole = _workspace(hb, opt)
+    whole.tile_stats.zero_()
+    whole.run()
+    st_all, _, _ = whole.fetch()
+    assert (st_all == want[0]).all()
+    rows = _tile_stats(whole, T, nb)
+    assert rows[:, t0:t1].any() and (part[:, t0:t1] == rows[:, t0:t1]).all()
+    assert not part[:, :t0].any()                     # (the range's run wrote no other tile's row)

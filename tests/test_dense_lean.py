@@ -14,10 +14,11 @@ exactly S2C_DPC_NOPS_MAX = 127 slots built here is checked to be long, in no den
 tile runs through k_tile — and its op words not in the block), windows with no rare piece, and
 largest lane counts of 15 | 16 (2 → 3 plane pairs) and 63 | 64 (3 → 4) on the 64-word instantiation
 and 16 and 64 on the 32-word one, each checked on the host to land on its side of the edge; in
-the count cases the exchange's bytes exceed the window's.  On the GPU, for each edge case: the
-extension's run gives the batch model's statistics, offsets and bytes and the oracle's files,
-twice on one workspace and once through a tile range, and s2c_run (the compact records' walk)
-gives the same on the same workspace."""
+the count cases the exchange's bytes exceed the window's; s2c_run / s2c_pileup refuse a batch
+that would launch k_tile_dense (dense tiles, a one-char fill) and take one that would not (a
+longer fill over built dense layers).  On the GPU, for each edge case: the run gives the batch
+model's statistics, offsets and bytes and the oracle's files, twice on one workspace and once
+through a tile range."""
 import ctypes as C
 import functools
 import random
@@ -210,10 +211,7 @@ def test_edge_cases_land_on_their_side(name):
         assert hb.dext[0, 7] > 0
 
 
-def _lean_of(hb):
-    y = L.DenseLean()
-    L.check(L.lib.s2c_batch_dense_lean_get(hb._b, C.byref(y)))
-    return y
+_lean_of = tde._lean_of
 
 
 def test_run_lean_refuses_a_malformed_lean_part_before_launch():
@@ -236,20 +234,56 @@ def test_run_lean_refuses_a_malformed_lean_part_before_launch():
             y = _lean_of(hb)
             setattr(y, field, val)
             assert f(C.byref(d), C.byref(x), C.byref(y), None) == L.S2C_ERR_ARG, field
-    # the extension without its lean part, through the older entries
-    for f in (L.lib.s2c_run_ext, L.lib.s2c_pileup_ext):
-        assert f(C.byref(d), C.byref(tde._ext_of(hb)), None) == L.S2C_ERR_ARG and "s2c_dense_lean" in L.last_error()
+
+
+def test_run_and_pileup_refuse_a_batch_that_needs_the_extension():
+    """s2c_run / s2c_pileup (no extension) on dense tiles with a one-char fill: S2C_ERR_ARG naming
+    the entries to call, over host pointers (never dereferenced: nothing is launched); so do the
+    _lean entries given neither part.  s2c_dev's own guards still come first."""
+    _, _, hb, _, _ = tde._case("dels_maxdel_on")
+    hb.ensure_layers()
+    d, keep = _host_dev(hb)
+    assert d.n_dense > 0 and d.fill_len == 1
+    for f, entry in ((L.lib.s2c_run, "s2c_run_lean"), (L.lib.s2c_pileup, "s2c_pileup_lean")):
+        assert f(C.byref(d), None) == L.S2C_ERR_ARG
+        assert entry in L.last_error() and "s2c_dense_ext" in L.last_error()
+        bad = L.Dev.from_buffer_copy(d)
+        bad.n_thr = 0
+        assert f(C.byref(bad), None) == L.S2C_ERR_ARG and "no thresholds" in L.last_error()
+    for f in (L.lib.s2c_run_lean, L.lib.s2c_pileup_lean):
+        assert f(C.byref(d), None, None, None) == L.S2C_ERR_ARG and "s2c_pileup_lean" in L.last_error()
+
+
+def test_pileup_takes_a_longer_fill_over_dense_layers_without_the_extension():
+    """With -f NN and the dense tiles' layers built, k_tile takes the dense tiles: s2c_pileup does
+    not ask for the extension.  Nothing is launched here: the s2c_dev claims 2^31 dense tiles, which
+    the launch's own limit refuses on the host — after every argument check, the refusal included —
+    while the same s2c_dev with a one-char fill is refused for its missing extension first."""
+    sam, opt, _, _, _ = tde._case("dels_maxdel_on")
+    hb = batch.parse_text(sam, opt.maxdel_active, 150)
+    try:
+        hb.ensure_layers(True)
+        assert hb.info.n_dense > 0 and hb.info.layers_dense == 1
+        d, keep = _host_dev(hb, fill=b"NN")
+        d.n_dense = 1 << 31
+        assert L.lib.s2c_pileup(C.byref(d), None) == L.S2C_ERR_LIMIT
+        assert "too many work items" in L.last_error() and "s2c_pileup_lean" not in L.last_error()
+        d, keep = _host_dev(hb, fill=b"N")
+        d.n_dense = 1 << 31
+        assert L.lib.s2c_pileup(C.byref(d), None) == L.S2C_ERR_ARG and "s2c_pileup_lean" in L.last_error()
+    finally:
+        hb.free()
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", list(EDGE))
 def test_edge_cases_on_the_gpu(name):
     _, opt, hb, want, ref = _edge(name)
-    ws, run_new, run_old, keep = tde._both_paths(hb, opt)
+    ws = tde._workspace(hb, opt)
     assert ws.lean.pairs == hb.lean_pairs and ws.lean.lds == hb.lean_lds
-    for run in (run_new, run_new, run_old):                 # the extension twice on one workspace, then s2c_run
+    for _ in range(2):                                      # twice on one workspace
         ws.out.zero_(), ws.tile_stats.zero_(), ws.blk_len.zero_()
-        run()
+        ws.run()
         st, offs, out = ws.fetch()
         assert (st == want[0]).all()
         assert (offs == want[1]).all()
@@ -258,13 +292,13 @@ def test_edge_cases_on_the_gpu(name):
     # ... and through a tile range: every tile but the first (a batch of one tile: that tile)
     nb, T = int(hb.info.n_tiles), len(opt.thresholds)
     t0, t1 = (1, nb) if nb > 1 else (0, 1)
-    ws, run_new, run_old, keep = tde._both_paths(hb, opt, tile_range=(t0, t1))
+    ws = tde._workspace(hb, opt, tile_range=(t0, t1))
     assert ws.lean.n_row == ws.ext.n_dext == ws.dev.n_dense == int(((hb.dwin[:, 0] >= t0) & (hb.dwin[:, 0] < t1)).sum()) > 0
     wo = want[1].astype(np.int64)
     body = b"".join(bytes(want[2][wo[t * nb + t0]:wo[t * nb + t1]]) for t in range(T))
     lens = np.concatenate([np.diff(wo)[t * nb + t0:t * nb + t1] for t in range(T)])
     ws.out.zero_(), ws.tile_stats.zero_(), ws.blk_len.zero_()
-    run_new()
+    ws.run()
     st, offs, out = ws.fetch()
     assert (np.diff(offs.astype(np.int64)) == lens).all()
     assert bytes(out) == body

@@ -1,7 +1,7 @@
-"""k_tile_dense's walk on hand-written SAMs: the lean path of the one-token reads (with their
-'N' offsets), the compacted pass of every other piece (deletion reads, '-' in SEQ, clipped and
-wrapped reads), more rare pieces than a wave's lanes, windows past the register-loaded piece
-records, and a last tile that ends mid-word.
+"""k_tile_dense's walk on hand-written SAMs: the one-token reads (with their 'N' offsets), the
+rare pass over every other piece (deletion reads, '-' in SEQ, clipped and wrapped reads), more
+rare pieces than a tile's threads, windows of more than 256 pieces, and a last tile that ends
+mid-word.
 
 Each case is checked twice: without a GPU, that its plan puts the stated feature into a dense
 window and that the batch model equals the oracle on it; on the GPU, that the device pipeline
@@ -19,7 +19,8 @@ from sam2consensus_amd import _lib as L
 from sam2consensus_amd import batch
 
 OP_M, OP_D, OP_N, OP_S, OP_H, OP_P, OP_EQ, OP_X = 0, 2, 3, 4, 5, 6, 7, 8   # s2c.h S2C_OP_*
-WT, WGD, PFN = 128, 64, 2   # k_tile_dense: threads per tile, lanes per wave, piece records per thread in registers
+WT, WGD = 128, 64   # k_tile_dense: threads per tile, lanes per wave
+BIG_WINDOW = 256    # pieces: big_window's windows hold more, with rare and 'N' pieces past that index
 
 
 def _bases(rng, p, n):
@@ -122,7 +123,7 @@ def _many_dels(rng):
 
 
 def _many_dels_x(rng):
-    """As _many_dels with every read holding three 'N': the X runs never fit the queue."""
+    """As _many_dels with every read holding three 'N': every read queues its X runs."""
     reads = []
     for i, p in enumerate(range(1, 1500)):
         reads.append((p, "12M%dD12M" % (1 + i % 6), _put(_bases(rng, p, 24), [1, 13, 22], "N")))
@@ -130,9 +131,8 @@ def _many_dels_x(rng):
 
 
 def _big_window(rng):
-    """Windows of more than WT·PFN = 256 pieces: a one-token read at every position (some with
-    'N'), a deletion read and a read with '-' in SEQ here and there (the compacted pass loads
-    their records too)."""
+    """Windows of more than 256 pieces: a one-token read at every position (some with 'N'), a
+    deletion read and a read with '-' in SEQ here and there."""
     reads = []
     for i, p in enumerate(range(1, 1900)):
         s = _bases(rng, p, 30)
@@ -227,47 +227,12 @@ def _ops(hb, k):
 
 
 def _is_del_read(hb, k, fl, nops):
-    """The compacted pass's deletion-read case: bases, D / N / P, bases and no other flag."""
+    """The rare pass's deletion-read case: bases, D / N / P, bases and no other flag."""
     if nops != 3 or fl & ~(L.S2C_PF_X | L.S2C_PF_DASH | L.S2C_PF_XFEW):
         return False
     (a, _), (b, _), (c, _) = _ops(hb, k)
     bases, dash = (OP_M, OP_EQ, OP_X), (OP_D, OP_N, OP_P)
     return a in bases and b in dash and c in bases
-
-
-def _queue_model(hb, w, k, fl, nops):
-    """The capacity rule of the wave queues (s2c_dense.hip) replayed on one window: per wave,
-    (rare pieces, rounds whose X runs were queued, rounds that fell back to the general walk)."""
-    npc = len(k)
-    nitw = (npc + WT - 1) // WT
-    qcap = WGD * nitw
-    res = []
-    for wv in range(WT // WGD):
-        mine = [i for it in range(nitw) for i in range(WT * it + WGD * wv, min(WT * it + WGD * wv + WGD, npc))]
-        rare = [i for i in mine if not fl[i] & L.S2C_PF_SIMPLE]
-        nx = sum(1 for i in mine if fl[i] & L.S2C_PF_SIMPLE and fl[i] & L.S2C_PF_X and not fl[i] & L.S2C_PF_XFEW)
-        nslow, queued, fell = len(rare), 0, 0
-        assert nslow + nx <= qcap
-        for base in range(0, nslow, WGD):
-            add = 0
-            for i in rare[base:base + WGD]:
-                if _is_del_read(hb, int(k[i]), int(fl[i]), int(nops[i])) and fl[i] & L.S2C_PF_X and not fl[i] & L.S2C_PF_XFEW \
-                        and not (fl[i] & L.S2C_PF_DASH and hb.maxdel_active):
-                    (_, l), _, (_, l2) = _ops(hb, int(k[i]))
-                    slen = int(hb.pc[int(k[i]), 3]) & 0xFFFFFF
-                    add += 1 + (1 if l < slen and min(l2, slen - l) > 0 else 0)
-            # the kernel's rule: the back stays above the front entries of later rounds
-            room = qcap - (nslow if base + WGD < nslow else 0)
-            if add and nx + add > room:
-                fell += 1
-            elif add:
-                queued += 1
-                # the entries written, [qcap − nx − add, qcap − nx), hold no front entry still to be read
-                unread = range(base + WGD, nslow)
-                assert not set(range(qcap - nx - add, qcap - nx)) & set(unread) and qcap - nx - add >= 0
-                nx += add
-        res.append((nslow, queued, fell))
-    return res
 
 
 def _check_plan(name, hb):
@@ -321,22 +286,16 @@ def _check_plan(name, hb):
                 empty2 += l >= slen
         assert few and xq and cross and at and above and empty2
     elif name.startswith("many_dels"):
-        loops = queued = fell = 0
+        # (the X-run queue of these two cases: test_dense_ext.test_x_run_queue_stays_inside_its_capacity)
         for w, k, fl, nops, pos, px in wins:
             assert all(_is_del_read(hb, int(k[i]), int(fl[i]), int(nops[i])) for i in range(len(k)))
             assert int(w[7] - w[6]) == len(k) and (hb.dpc[w[12]:w[12] + len(k), 1] >> 24 == fl).all()
-            for nslow, q, f in _queue_model(hb, w, k, fl, nops):
-                loops += nslow > WGD
-                queued += q
-                fell += f
-        assert loops and fell
-        assert queued or name == "many_dels_x"
     elif name == "big_window":
         npw = hb.dwin[:, 7].astype(np.int64) - hb.dwin[:, 6]
-        assert (npw > WT * PFN).any()
+        assert (npw > BIG_WINDOW).any()
         late_rare = late_n = 0
         for w, k, fl, nops, pos, px in wins:
-            late = np.arange(len(k)) >= WT * PFN
+            late = np.arange(len(k)) >= BIG_WINDOW
             late_rare += int((late & ((fl & S) == 0)).sum())
             late_n += int((late & ((fl & S) != 0) & ((fl & F) != 0)).sum())
         assert late_rare and late_n
