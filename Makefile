@@ -14,7 +14,7 @@ LINK     = $(HIPCC) -shared -fPIC --offload-arch=$(ARCH) $^ -lz -lpthread -o $@
 # the one list of host sources (every csrc/*.cpp) and of kernel sources
 HOSTSRC  = $(wildcard $(SRC)/*.cpp)
 HOSTOBJ  = $(HOSTSRC:$(SRC)/%.cpp=$(BUILD)/%.o)
-KERNELS  = s2c_reads s2c_tile s2c_dense s2c_bodies s2c_table s2c_sites s2c_runs s2c_ins s2c_links
+KERNELS  = s2c_reads s2c_tile s2c_dense s2c_bodies s2c_table s2c_sites s2c_runs s2c_ins s2c_links s2c_dels
 KOBJ     = $(KERNELS:%=$(BUILD)/%.o)
 
 all: $(OUT)

@@ -33,9 +33,11 @@
  *          (4) k_consensus: tiles whose depth or insertion layout exceeds one workgroup;
  *          (5) the tables as text, formatted where the counts and the insertion events are:
  *              k_table_* (--counts), k_sites_* (--variants), k_runs_* (--depth, --lowcov),
- *              k_ins_* (--insertions: the motifs of (3) grouped, ordered and printed per tile) and
+ *              k_ins_* (--insertions: the motifs of (3) grouped, ordered and printed per tile),
  *              k_links_* (--links: one more walk of every piece, against the mask of the mixed
- *              sites, counts the symbol pairs fragments carry across neighbouring sites).
+ *              sites, counts the symbol pairs fragments carry across neighbouring sites) and
+ *              k_dels_* (--deletions: two walks of every piece merge the D / N / P runs it
+ *              carries into a table of distinct events, bucketed, ordered and printed per tile).
  */
 #ifndef S2C_H
 #define S2C_H
@@ -768,6 +770,80 @@ int s2c_links_len(const uint64_t *mask, const uint32_t *rank, int64_t padded_len
 int s2c_links_write(const uint64_t *mask, const uint32_t *rank, int64_t padded_len, const uint32_t *pairs, int64_t n_sites,
                     const int64_t *blocks, const int64_t *refs, const int64_t *offs, int64_t n, int64_t min_reads,
                     uint8_t *dst, int64_t dst_len, void *stream);
+
+/* Gap events as text (the CLI's --deletions; csrc/s2c_dels.hip): one table per run.  A fragment is
+ * a piece of the batch, seqout[ka, kb) of its read — for a read over maxdel (:210) the host has cut
+ * that range to its first and last counted character.  A gap character is a character of seqout
+ * that a D, N or P token produced (:70-72; a '-' of SEQ is a base); an event is a maximal run of
+ * consecutive gap characters inside one fragment, {g, len}: its first global position and its
+ * length.  Tokens that add nothing to seqout (I, S, H, an M after SEQ ran out) do not split a
+ * run; a base does; the POS <= 0 wrap does (two pieces).  Events are clamped to padded_len
+ * (< 2^32); one at or past it is none.
+ *   s2c_dels_count    walks every piece (pc of n_pieces + 1 records and ops of n_ops words as
+ *                     s2c_dev's; a piece's op words are cut at n_ops) and ADDS its events to
+ *                     *n_events (device u64, zeroed by the caller): the total E, which the host
+ *                     reads to size the rest.  It reads no planes: which reads are dropped shows
+ *                     in the pieces' ranges already.
+ *   s2c_dels_collect  the same walk ADDS every event to slots = u32 [n_slots][4] {g, len, reads,
+ *                     dropped}, an open-addressing table the caller zeroed, 16-byte aligned,
+ *                     n_slots a power of two (>= 2 E keeps the probes short): the 64-bit key
+ *                     {g, len} is claimed by compare-and-swap (len >= 1, so zero is the empty
+ *                     slot), reads += 1 and, for a piece of a read over maxdel (maxdel_active /
+ *                     maxdel as s2c_dev's, the '-' of SEQ counted from the planes bq / bx of
+ *                     n_qwords words), dropped += 1.  Integer adds: the table's content does not
+ *                     depend on order, only its slot layout does.  An event probes at most
+ *                     n_slots slots; one that finds none sets *overflow (device u32, zeroed by the
+ *                     caller) to 1 and is lost — the caller must check it.  No store lies
+ *                     outside slots[0, n_slots) and *overflow.
+ *   s2c_dels_tiles    tcount[t] += the slots that hold an entry of tile t (u32 [n_tiles], zeroed
+ *                     by the caller): len >= 1, g >> 5 < n_words and t = wtile[g >> 5] < n_tiles
+ *                     (wtile as s2c_dev's, from word 0).  The caller's exclusive prefix sum is
+ *                     tstart (int64 [n_tiles + 1]).
+ *   s2c_dels_scatter  those slots copied to ent = u32 [n_ent][4], tile t's at [tstart[t],
+ *                     tstart[t+1]) in any order (cursor: u32 [n_tiles], zeroed by the caller).  A
+ *                     tile whose range is negative, decreasing or past n_ent gets none, and a
+ *                     tile's range takes no more than it holds.
+ *   s2c_dels_len, s2c_dels_write   the two passes of the other tables, tile i with block i of the
+ *                     count tables' blocks {a, b, p0} (valid as s2c_table_len's) and the reference
+ *                     tiles[i][2] (tiles = [n_tiles][S2C_TILE_WORDS]; only that word is read),
+ *                     whose name is names[nametab[2 r], + nametab[2 r + 1]) — a byte blob of
+ *                     names_len bytes and int64 [n_refs][2] {offset, length}; names hold no
+ *                     whitespace (:163).  An entry of tile i is listed iff len >= 1, reads >=
+ *                     min_reads (1 <= min_reads < 2^32) and a <= g < min(b, a + S2C_TILE_MAX): its
+ *                     line "REF\tSTART\tEND\tLEN\tREADS\tDROPPED\tCOV\n" with START = p0 + (g − a),
+ *                     END = START + LEN − 1 (it may lie in a later block) and COV the 64-bit sum of
+ *                     the six counts at g, plain decimal.  A tile's lines are ordered by START, then
+ *                     LEN, rising — a total order over distinct events, so the bytes depend neither
+ *                     on slots nor on arrival; equal keys of a hand-built table keep their order
+ *                     in ent.  s2c_dels_len orders tile i's listed entries through tmp (scratch, u32
+ *                     [n_ent][4]) back into the front of its part of ent, writes their number to
+ *                     tn[i] (u32 [n_tiles]) and the exact bytes of their lines to lens[i]; the
+ *                     caller forms offs[n + 1]; s2c_dels_write, given the same ent, tstart and tn,
+ *                     writes them to dst[offs[i], offs[i+1]) and no byte outside it.  A tile
+ *                     whose tstart range is negative, decreasing or past n_ent, whose block is
+ *                     outside the bounds, whose reference is >= n_refs or whose name lies outside
+ *                     the blob gets lens[i] = 0 and tn[i] = 0 and nothing of it is touched;
+ *                     s2c_dels_write skips those and a tile with offs[i] < 0, offs[i+1] < offs[i]
+ *                     or offs[i+1] > dst_len, and checks every entry again before it reads counts.
+ *                     ent and tmp are 16-byte aligned; n_ent < 2^32.
+ * Every loop is bounded by a checked length.  All six are asynchronous on stream and allocate
+ * nothing; they write no array of the batch and add no struct field (ABI 14 stands). */
+int s2c_dels_count(const uint32_t *pc, const uint32_t *ops, int64_t n_pieces, int64_t n_ops, int64_t padded_len,
+                   uint64_t *n_events, void *stream);
+int s2c_dels_collect(const uint32_t *pc, const uint32_t *ops, const uint32_t *bq, const uint32_t *bx, int64_t n_pieces,
+                     int64_t n_ops, int64_t n_qwords, int maxdel_active, int maxdel, int64_t padded_len, uint32_t *slots,
+                     int64_t n_slots, uint32_t *overflow, void *stream);
+int s2c_dels_tiles(const uint32_t *slots, int64_t n_slots, const uint32_t *wtile, int64_t n_words, int64_t n_tiles,
+                   uint32_t *tcount, void *stream);
+int s2c_dels_scatter(const uint32_t *slots, int64_t n_slots, const uint32_t *wtile, int64_t n_words, int64_t n_tiles,
+                     const int64_t *tstart, uint32_t *cursor, uint32_t *ent, int64_t n_ent, void *stream);
+int s2c_dels_len(uint32_t *ent, uint32_t *tmp, int64_t n_ent, const int64_t *tstart, const uint32_t *tiles, int64_t n_tiles,
+                 const int64_t *blocks, const uint8_t *names, int64_t names_len, const int64_t *nametab, int64_t n_refs,
+                 const uint32_t *counts, int64_t padded_len, int64_t min_reads, uint32_t *tn, int64_t *lens, void *stream);
+int s2c_dels_write(const uint32_t *ent, int64_t n_ent, const int64_t *tstart, const uint32_t *tn, const uint32_t *tiles,
+                   int64_t n_tiles, const int64_t *blocks, const uint8_t *names, int64_t names_len, const int64_t *nametab,
+                   int64_t n_refs, const uint32_t *counts, int64_t padded_len, const int64_t *offs, uint8_t *dst,
+                   int64_t dst_len, void *stream);
 
 /* Diagnostics (tests only, not part of the product path): k_reads over every piece, then
  * every tile's counts stored to d->counts ([6][padded_len] u32) and no vote. */

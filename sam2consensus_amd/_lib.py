@@ -141,6 +141,7 @@ EXPORTS = [
     "s2c_runs_mark", "s2c_runs_len", "s2c_runs_write",
     "s2c_ins_len", "s2c_ins_write",
     "s2c_links_pop", "s2c_links_count", "s2c_links_len", "s2c_links_write",
+    "s2c_dels_count", "s2c_dels_collect", "s2c_dels_tiles", "s2c_dels_scatter", "s2c_dels_len", "s2c_dels_write",
 ]
 
 
@@ -240,6 +241,15 @@ def _load():
         "s2c_links_len": (C.c_int, [_VP, _VP, C.c_int64, _VP, C.c_int64, _VP, _VP, C.c_int64, C.c_int64, _VP, _VP]),
         "s2c_links_write": (C.c_int, [_VP, _VP, C.c_int64, _VP, C.c_int64, _VP, _VP, _VP, C.c_int64, C.c_int64, _VP, C.c_int64,
                                       _VP]),
+        "s2c_dels_count": (C.c_int, [_VP, _VP, C.c_int64, C.c_int64, C.c_int64, _VP, _VP]),
+        "s2c_dels_collect": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int64, _VP,
+                                       C.c_int64, _VP, _VP]),
+        "s2c_dels_tiles": (C.c_int, [_VP, C.c_int64, _VP, C.c_int64, C.c_int64, _VP, _VP]),
+        "s2c_dels_scatter": (C.c_int, [_VP, C.c_int64, _VP, C.c_int64, C.c_int64, _VP, _VP, _VP, C.c_int64, _VP]),
+        "s2c_dels_len": (C.c_int, [_VP, _VP, C.c_int64, _VP, _VP, C.c_int64, _VP, _VP, C.c_int64, _VP, C.c_int64, _VP, C.c_int64,
+                                   C.c_int64, _VP, _VP, _VP]),
+        "s2c_dels_write": (C.c_int, [_VP, C.c_int64, _VP, _VP, _VP, C.c_int64, _VP, _VP, C.c_int64, _VP, C.c_int64, _VP, C.c_int64,
+                                     _VP, _VP, C.c_int64, _VP]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)

@@ -95,6 +95,17 @@ def build_parser():
                         "Not available with more than one process or with S2C_STREAM")
     p.add_argument("--min-link-reads", action="store", dest="min_link_reads", type=int, default=None, metavar="N",
                    help="With --links: list a pair of sites only when at least N reads observe both, default=1")
+    p.add_argument("--deletions", action="store_true", dest="deletions", default=False,
+                   help="Also write one PREFIX.deletions.tsv in the output folder: one line ref, start, end, len, reads, "
+                        "dropped, cov (tab-separated, positions 1-based and inclusive) per distinct gap event the reads "
+                        "carry, a maximal run of D, N and P characters inside a read, or inside one of its two parts "
+                        "around the POS <= 0 wrap (I, S and H between two of them do not split it, a base does): the "
+                        "reads that carry exactly this event, those among them whose gaps the -d rule kept out of the "
+                        "counts (0 everywhere when -d is given), and the coverage at start; ordered by reference, "
+                        "start and len; independent of -c, -m, -f and -n. "
+                        "Not available with more than one process or with S2C_STREAM")
+    p.add_argument("--min-del-reads", action="store", dest="min_del_reads", type=int, default=None, metavar="N",
+                   help="With --deletions: list an event only when at least N reads carry it, default=1")
     return p
 
 
@@ -159,6 +170,23 @@ def insertions_of(parser, args):
     return n
 
 
+MIN_DEL_READS = 1
+
+
+def deletions_of(parser, args):
+    """min_reads of --deletions or None; --min-del-reads outside [1, 2^32) or without --deletions
+    is the parser's error (exit status 2)."""
+    n = args.min_del_reads
+    if not args.deletions:
+        if n is not None:
+            parser.error("--min-del-reads needs --deletions")
+        return None
+    n = MIN_DEL_READS if n is None else n
+    if not 1 <= n < 2 ** 32:
+        parser.error("--min-del-reads must be at least 1 and below 2^32")
+    return n
+
+
 def tables_of(parser, args):
     """The tables the flags ask for as ``table.request``'s mapping: ``counts``, ``depth`` and
     ``lowcov`` without parameters, the others with what ``variants_of``, ``insertions_of`` and
@@ -186,7 +214,8 @@ class RunResult:
 LEAST_FIRST = ("variants", "depth", "lowcov", "links")
 
 
-def consensus_batch(hb, thresholds, prefix, min_depth=1, fill=b"-", nchar=0, device=None, timings=None, **tables):
+def consensus_batch(hb, thresholds, prefix, min_depth=1, fill=b"-", nchar=0, device=None, timings=None, deletions=None,
+                    **tables):
     """Device pipeline on a parsed HostBatch → {``REF__PREFIX.fasta``: bytes}.  ``tables``: the
     text tables to add, by the keys of ``table.TABLES`` (``table.request`` normalises them) —
     ``counts``, ``depth``, ``lowcov`` = True, ``variants`` = (min_alt, min_frac), ``insertions`` =
@@ -194,7 +223,9 @@ def consensus_batch(hb, thresholds, prefix, min_depth=1, fill=b"-", nchar=0, dev
     ``depth``'s ``passed`` and ``lowcov``'s cut take the least coverage max(min_depth, 1).  Their
     ``REF__PREFIX<suffix>`` files follow the FASTA entries table by table in ``TABLES`` order, the
     one ``PREFIX.depth_summary.tsv`` of ``depth`` where ``table.SUMMARY_AFTER`` puts it — the run
-    then takes the counts route (``Workspace.run_with_tables``)."""
+    then takes the counts route (``Workspace.run_with_tables``).  ``deletions`` = min_reads adds the
+    run's one ``PREFIX.deletions.tsv`` (``table.deletions_file``) after every other file; alone it
+    takes the counts route too."""
     import torch
 
     from .engine import _UPLOADERS, DeviceBatch, Workspace, needs_dense_layers, to_host
@@ -203,9 +234,11 @@ def consensus_batch(hb, thresholds, prefix, min_depth=1, fill=b"-", nchar=0, dev
     t = timings if timings is not None else {}
     t0 = time.perf_counter()
     req = table.request(**tables)
-    db = DeviceBatch(hb, device, dense_layers=needs_dense_layers(fill, bool(req)))
+    dels = None if deletions is None or deletions is False else (MIN_DEL_READS if deletions is True else int(deletions))
+    route = bool(req) or dels is not None   # (the counts route: every tile's counts kept for the tables)
+    db = DeviceBatch(hb, device, dense_layers=needs_dense_layers(fill, route))
     t1 = time.perf_counter()
-    ws = Workspace(db, thresholds, min_depth, fill, keep_counts=bool(req))
+    ws = Workspace(db, thresholds, min_depth, fill, keep_counts=route)
     torch.cuda.synchronize(db.device)
     t["h2d"] = time.perf_counter() - t0
     t["h2d_issue"] = t1 - t0   # (layers + pinned staging + copies issued; the rest: workspace + drain)
@@ -214,9 +247,9 @@ def consensus_batch(hb, thresholds, prefix, min_depth=1, fill=b"-", nchar=0, dev
         t.update(("h2d_up_" + k, v) for k, v in up.timing.items())
     t0 = time.perf_counter()
     res = {}
-    if req:
+    if route:
         least = (max(int(min_depth), 1),)
-        res = ws.run_with_tables({k: (least if k in LEAST_FIRST else ()) + v for k, v in req.items()})
+        res = ws.run_with_tables({k: (least if k in LEAST_FIRST else ()) + v for k, v in req.items()}, deletions=dels)
     else:
         ws.run()
     torch.cuda.synchronize(db.device)
@@ -232,6 +265,8 @@ def consensus_batch(hb, thresholds, prefix, min_depth=1, fill=b"-", nchar=0, dev
         if tab.key == table.SUMMARY_AFTER and "depth" in res:
             # (the summary: the host sums the tiles' statistics; it never reads the counts)
             files.update(table.summary_file(hb, prefix, res["depth"][2]))
+    if table.DEL_KEY in res:   # (the run's one deletion table: last)
+        files.update(table.deletions_file(hb, prefix, res[table.DEL_KEY][0], to_host(res[table.DEL_KEY][1])))
     t["format"] = time.perf_counter() - t0
     return files
 
@@ -337,9 +372,10 @@ def consensus_batch_hip(sess, hb, thresholds, prefix, min_depth=1, fill=b"-", nc
     return files
 
 
-def _consensus_files_tables(filename, thresholds, prefix, min_depth, fill, nchar, maxdel_active, device, log, req):
-    """consensus_files with the tables of ``req`` (table.request): the torch engine path
-    (consensus_batch)."""
+def _consensus_files_tables(filename, thresholds, prefix, min_depth, fill, nchar, maxdel_active, device, log, req,
+                            deletions=None):
+    """consensus_files with the tables of ``req`` (table.request) and the deletion table: the
+    torch engine path (consensus_batch)."""
     import torch
 
     from . import _lib
@@ -364,20 +400,22 @@ def _consensus_files_tables(filename, thresholds, prefix, min_depth, fill, nchar
     t["parse"] = time.perf_counter() - t0
     if log:
         _log_summary(log, hb.info)
-    files = consensus_batch(hb, thresholds, prefix, min_depth, fill, nchar, dev, t, **req)
+    files = consensus_batch(hb, thresholds, prefix, min_depth, fill, nchar, dev, t, deletions=deletions, **req)
     return RunResult(files, t, hb.info, hb.free_async())
 
 
 def consensus_files(filename, thresholds, prefix, min_depth=1, fill=b"-", nchar=0, maxdel_active=True,
-                    device=None, log=None, **tables):
+                    device=None, log=None, deletions=None, **tables):
     """Run the whole pipeline on one SAM/SAM.gz file; returns a RunResult whose
     ``files`` maps ``REF__PREFIX.fasta`` → content bytes (nothing written).  The device side
     runs through the HIP runtime directly (hiprun.py): this path never imports PyTorch.
     With any of ``consensus_batch``'s ``tables`` the files also hold those tables, and the run
-    goes through the torch engine path instead (``consensus_batch``)."""
+    goes through the torch engine path instead (``consensus_batch``); so it does with
+    ``deletions`` = min_reads, which adds the run's ``PREFIX.deletions.tsv``."""
     req = table.request(**tables)
-    if req:
-        return _consensus_files_tables(filename, thresholds, prefix, min_depth, fill, nchar, maxdel_active, device, log, req)
+    if req or (deletions is not None and deletions is not False):
+        return _consensus_files_tables(filename, thresholds, prefix, min_depth, fill, nchar, maxdel_active, device, log, req,
+                                       deletions)
     from .batch import Parser
     from .hiprun import Session, device_index
 
@@ -409,22 +447,25 @@ def consensus_files(filename, thresholds, prefix, min_depth=1, fill=b"-", nchar=
     return RunResult(files, t, hb.info, hb.free_async())
 
 
-def run_text(sam_text, argv, device=None, **tables):
+def run_text(sam_text, argv, device=None, deletions=None, **tables):
     """Library entry for tests: SAM text + CLI args (without -i) → (status, {fname: str}).
     status is "ok" or the reference's exception class name; nothing touches the disk.
     ``tables``: ``consensus_batch``'s; a table given among the args (``--variants`` and its
-    options, ...) is added, and wins over its keyword."""
+    options, ...) is added, and wins over its keyword; so do ``deletions`` = min_reads and
+    ``--deletions`` / ``--min-del-reads``."""
     from .batch import parse_text
 
     parser = build_parser()
     args = parser.parse_args(["-i", "in.sam"] + list(argv))
     req = {**table.request(**tables), **tables_of(parser, args)}
+    dels = deletions_of(parser, args)
+    dels = deletions if dels is None else dels
     try:
         thresholds = [float(i) for i in args.thresholds.split(",")]
         prefix = args.prefix or "in"
         hb = parse_text(sam_text, not isinstance(args.maxdel, str), 150)
         files = consensus_batch(hb, thresholds, os.fsencode(prefix), args.min_depth,
-                                os.fsencode(args.fill), args.n, device, **req)
+                                os.fsencode(args.fill), args.n, device, deletions=dels, **req)
     except (KeyError, IndexError, ValueError, ZeroDivisionError, OverflowError) as e:
         return type(e).__name__, {}
     return "ok", {k.decode("latin-1"): v.decode("latin-1") for k, v in files.items()}
@@ -492,7 +533,8 @@ def main(argv=None):
     parser = build_parser()
     args = parser.parse_args(argv)
     req = tables_of(parser, args)
-    for key in req:   # (refused before a folder is made or a device touched)
+    dels = deletions_of(parser, args)
+    for key in list(req) + ([table.DEL_KEY] if dels is not None else []):   # (refused before a folder is made or a device touched)
         if _dist_env()[0] > 1:
             parser.error("--" + key + " is not available with more than one process (WORLD_SIZE > 1)")
         if os.environ.get("S2C_STREAM"):
@@ -526,16 +568,18 @@ def main(argv=None):
                                              batch_bytes=sb).files
         else:
             res = consensus_files(filename, thresholds, os.fsencode(prefix), args.min_depth,
-                                  os.fsencode(args.fill), args.n, maxdel_active, log=lambda s: print(s), **req)
+                                  os.fsencode(args.fill), args.n, maxdel_active, log=lambda s: print(s), deletions=dels, **req)
             files = res.files
-    tables = []
+    tables, last = [], None
     for fname, body in files.items():                                             # :411-424
         path = os.fsencode(outfolder) + fname
         with open(path, "wb") as fh:
             fh.write(body)
         shown = os.fsdecode(path)
         noun = next((t.noun for t in table.TABLES if t.key in req and fname.endswith(t.suffix)), None)
-        if "depth" in req and fname.endswith(table.SUMMARY_SUFFIX):   # (PREFIX alone: no reference)
+        if dels is not None and fname == os.fsencode(prefix) + table.DEL_SUFFIX:   # (PREFIX alone; the files' last)
+            last = "Deletion table saved in: " + shown
+        elif "depth" in req and fname.endswith(table.SUMMARY_SUFFIX):   # (PREFIX alone: no reference)
             tables.append("Depth summary saved in: " + shown)
         elif noun is not None:   # (the tables' lines after the consensus lines, in the files' order)
             tables.append(noun + " saved for " + os.fsdecode(fname[: fname.rfind(b"__")]) + " in: " + shown)
@@ -545,7 +589,7 @@ def main(argv=None):
         else:
             print("Consensus sequences at " + ",".join([str(int(i * 100)) + "%" for i in thresholds]) +
                   " saved for " + os.fsdecode(fname[: fname.rfind(b"__")]) + " in: " + shown)
-    for line in tables:
+    for line in tables + ([last] if last is not None else []):
         print(line)
     if res is not None:
         res.wait()

@@ -16,7 +16,7 @@ import torch
 from . import _lib as L
 from ._lib import lib
 from .devargs import EXT_ARRAYS, LEAN_ARRAYS, UPLOAD, fill_dev, fill_ext, fill_lean
-from .table import TABLES
+from .table import DEL_KEY, TABLES
 
 
 def _dev(device):
@@ -388,7 +388,8 @@ class Workspace:
         keep_counts=True over the whole batch (every tile's counts in HBM) and counts a
         counts-only stage has filled —, then the method's ``own_checks()``, then on the current
         stream ``len_call(nt, blocks, lens, st)``, the launches that leave tile k's bytes in
-        ``lens[k]`` (it allocates what the method needs besides), the prefix sum, the one host
+        ``lens[k]`` (it allocates what the method needs besides; ``False`` from it: it launched
+        nothing and every length is zero), the prefix sum, the one host
         read of the offsets, and ``write_call(nt, blocks, offs, text, total, st)``, the launch
         that formats tile k into text[offs[k], offs[k+1]) (``blocks``: ``_table_blocks``; all
         buffers as pointers).  Returns (offs[n_tiles + 1] int64 numpy, device uint8 tensor of
@@ -408,7 +409,8 @@ class Workspace:
         blocks = _ptr(self._table_blocks())
         offs_d = torch.zeros(nt + 1, dtype=torch.int64, device=dev)
         lens = torch.empty(nt, dtype=torch.int64, device=dev)
-        len_call(nt, blocks, _ptr(lens), st)
+        if len_call(nt, blocks, _ptr(lens), st) is False:   # (it found nothing to format and left lens as it was)
+            lens.zero_()
         torch.cumsum(lens, 0, out=offs_d[1:])
         offs = offs_d.cpu().numpy()
         total = int(offs[-1])
@@ -570,7 +572,77 @@ class Workspace:
                                       blocks, _ptr(buf["scratch"]), offs, text, total, st))
         return self._two_pass("insertions_table", len_call, write_call, own_checks, filled_by="accumulate")
 
-    def run_with_tables(self, request):
+    def _ref_names(self):
+        """(device uint8 blob of the references' names, device int64 [n_refs][2] {offset, length},
+        the blob's bytes): uploaded once per workspace for ``deletions_table``'s lines."""
+        if getattr(self, "_names", None) is None:
+            raw = [n.encode("latin-1") for n in self.db.hb.names]
+            tab = np.zeros((max(len(raw), 1), 2), dtype=np.int64)
+            tab[:len(raw), 1] = [len(n) for n in raw]
+            tab[:len(raw), 0] = np.cumsum(tab[:len(raw), 1]) - tab[:len(raw), 1]
+            blob = np.frombuffer(b"".join(raw), dtype=np.uint8).copy()
+            self._names = (_up(blob, self.db.device), _up(tab.reshape(-1), self.db.device), int(blob.size))
+        return self._names
+
+    def deletions_table(self, min_reads=1):
+        """The gap events the batch's pieces carry as the text of the deletion table (table.py;
+        s2c_dels_count over every piece, the one 8-byte host read of the events' number E,
+        s2c_dels_collect into a table of 2^k >= 2 E slots, s2c_dels_tiles, the prefix sum and
+        s2c_dels_scatter into the tiles' parts of E entries, then s2c_dels_len, the prefix sum and
+        s2c_dels_write, on the current stream; the table, two arrays of E entries and three words
+        per tile are allocated here on every call, 64 to 96 bytes per event in all): the return shape
+        and the preconditions of ``counts_table`` — the lines of the events that start in tile k
+        at [offs[k], offs[k+1]), each with its reference's name, so the text is in file order.
+        ``min_reads`` >= 1: the least fragments of a listed event.  Without an event nothing
+        beyond the count is launched."""
+        db, i, buf = self.db, self.db.info, {}
+        Lp = i.padded_len
+
+        def own_checks():
+            if not 1 <= int(min_reads) < 2 ** 32:
+                raise ValueError("deletions_table: 1 <= min_reads < 2^32")
+            if int(i.word_lo) != 0:
+                raise ValueError("deletions_table needs the whole batch's per-word arrays")
+
+        def len_call(nt, blocks, lens, st):
+            dev, d = db.device, self.dev
+            i32 = lambda n: torch.zeros(max(int(n), 4), dtype=torch.int32, device=dev)  # noqa: E731
+            total = torch.zeros(1, dtype=torch.int64, device=dev)
+            L.check(lib.s2c_dels_count(_ptr(db.pc), _ptr(db.ops), int(i.n_pieces), int(i.n_ops), Lp, _ptr(total), st))
+            E = buf["E"] = int(total.item())
+            if E == 0:
+                return False
+            if E >= 2 ** 32:
+                raise L.S2CError(L.S2C_ERR_LIMIT, "more than 2^32 gap events")
+            ns = 1 << max((2 * E - 1).bit_length(), 1)
+            slots = torch.zeros(16 * ns, dtype=torch.uint8, device=dev)
+            over = buf["over"] = i32(1)
+            L.check(lib.s2c_dels_collect(_ptr(db.pc), _ptr(db.ops), _ptr(db.bq), _ptr(db.bx), int(i.n_pieces), int(i.n_ops),
+                                         int(i.n_qwords), int(d.maxdel_active), int(d.maxdel), Lp, _ptr(slots), ns, _ptr(over), st))
+            nw = int(i.word_hi)
+            tcount, cursor, tn = i32(nt), i32(nt), i32(nt)
+            tstart = torch.zeros(nt + 1, dtype=torch.int64, device=dev)
+            L.check(lib.s2c_dels_tiles(_ptr(slots), ns, _ptr(db.wtile), nw, nt, _ptr(tcount), st))
+            torch.cumsum(tcount[:nt], 0, dtype=torch.int64, out=tstart[1:])
+            ent = torch.empty(16 * E, dtype=torch.uint8, device=dev)
+            tmp = torch.empty(16 * E, dtype=torch.uint8, device=dev)
+            L.check(lib.s2c_dels_scatter(_ptr(slots), ns, _ptr(db.wtile), nw, nt, _ptr(tstart), _ptr(cursor), _ptr(ent), E, st))
+            names, tab, nbytes = self._ref_names()
+            buf["args"] = (_ptr(ent), E, _ptr(tstart), _ptr(tn), _ptr(db.tiles), nt, blocks, _ptr(names), nbytes, _ptr(tab),
+                           int(i.n_refs), _ptr(self.counts), Lp)
+            buf["keep"] = (ent, tmp, tstart, tn, slots)
+            L.check(lib.s2c_dels_len(_ptr(ent), _ptr(tmp), E, _ptr(tstart), _ptr(db.tiles), nt, blocks, _ptr(names), nbytes, _ptr(tab),
+                                     int(i.n_refs), _ptr(self.counts), Lp, int(min_reads), _ptr(tn), lens, st))
+
+        def write_call(nt, blocks, offs, text, total, st):
+            if not buf["E"]:
+                return
+            if int(buf["over"][0].item()):   # (only a table of too few slots fills)
+                raise L.S2CError(L.S2C_ERR_LIMIT, "deletions_table: the event table overflowed")
+            L.check(lib.s2c_dels_write(*buf["args"], offs, text, total, st))
+        return self._two_pass("deletions_table", len_call, write_call, own_checks)
+
+    def run_with_tables(self, request, deletions=None):
         """``run()`` through the counts route, with the tables of ``request`` (``table.request``'s
         mapping, a table's parameters those of its method): ``counts: ()``, ``variants: (min_cov,
         min_alt, min_frac)``, ``depth: (min_cov,)`` (``passed`` counted at min_cov), ``lowcov:
@@ -580,7 +652,9 @@ class Workspace:
         which leaves the counts zero and consumes the insertion tables), then every tile is voted
         from them (``vote_all``); ``fetch()`` yields the FASTA results as after ``run()``.  Returns
         {key: what the table's method returns} for exactly the keys of ``request``; a site rule
-        that ``variants`` and ``links`` share is marked once."""
+        that ``variants`` and ``links`` share is marked once.  ``deletions`` = min_reads (``True``:
+        1) adds the per-run deletion table, which is no entry of ``TABLES``: ``deletions_table``'s
+        pair under ``"deletions"``, formatted after the tables of ``request`` and before the vote."""
         if not self.keep_counts:
             raise ValueError("run_with_tables needs Workspace(keep_counts=True)")
         unknown = sorted(set(request) - {t.key for t in TABLES})
@@ -597,6 +671,8 @@ class Workspace:
         self._site_masks = {}
         try:
             res = {t.key: make[t.key](*request[t.key]) for t in TABLES if t.key in request}
+            if deletions is not None and deletions is not False:
+                res[DEL_KEY] = self.deletions_table(1 if deletions is True else int(deletions))
         finally:
             self._site_masks = None
         self.vote_all()

@@ -53,6 +53,20 @@ number of non-zero ``n[s1][s2]``, ``pairs`` those entries as ``XY:count`` joined
 count falling, then by ``(s1, s2)`` in ``-ACGNT`` order — a total order.  A pair is listed iff
 ``reads >= --min-link-reads`` (>= 1).  The device walks the reads and formats (csrc/s2c_links.hip,
 ``Workspace.links_table``); ``link_pairs`` and ``format_links`` are the model.
+
+The deletion table (``--deletions``): one ``PREFIX.deletions.tsv`` per run of the program, like
+the depth summary, one line ``ref\tstart\tend\tlen\treads\tdropped\tcov`` per distinct gap event.
+A gap character is a character of parsecigar's ``seqout`` that a ``D``, ``N`` or ``P`` token
+produced (:70-72; a ``-`` of SEQ is a base).  A read is dropped when the ``-d`` rule is active and
+``seqout.count("-") > 150`` (:210): its ``-`` are not counted.  A read's span runs from its first
+counted character to its last; a fragment is the span, or each of its two parts around the
+``POS <= 0`` wrap.  An event is a maximal run of consecutive gap characters inside one fragment
+— ``I``, ``S``, ``H`` and an ``M`` after SEQ ran out do not split it, a base does — keyed by
+(reference, start, len), 1-based and inclusive; ``reads`` the fragments that carry exactly it,
+``dropped`` those among them of dropped reads, ``cov`` the sum of the six counts at ``start``.
+Listed iff ``reads >= --min-del-reads``; ordered by reference in header order, ``start``, ``len``.
+The device walks, merges and formats (csrc/s2c_dels.hip, ``Workspace.deletions_table``);
+``gap_events`` and ``format_deletions`` are the model.
 """
 from __future__ import annotations
 
@@ -88,6 +102,11 @@ TABLES = (Table("counts", SUFFIX, HEADER, "Count table"),
           Table("insertions", INS_SUFFIX, INS_HEADER, "Insertion table"),
           Table("links", LINKS_SUFFIX, LINKS_HEADER, "Link table"))
 SUMMARY_AFTER = "lowcov"
+# The second file that is no per-reference table: the deletion table of a run, after every file
+# above (the flag --deletions, the stdout line "Deletion table saved in: PATH").
+DEL_HEADER = b"ref\tstart\tend\tlen\treads\tdropped\tcov\n"
+DEL_SUFFIX = b".deletions.tsv"
+DEL_KEY = "deletions"
 
 
 def request(**kw):
@@ -202,6 +221,53 @@ def format_links(pairs, site_positions, p0=1, min_reads=1):
         out.append("%d\t%d\t%d\t%d\t%s\n" % (int(p0) + int(site_positions[k]), int(p0) + int(site_positions[k + 1]), reads, len(e),
                                              ",".join("%s%s:%d" % (SYMBOLS[a], SYMBOLS[b], n) for n, a, b in e)))
     return "".join(out).encode("ascii")
+
+
+def gap_events(fragments):
+    """{(start, len): [reads, dropped]} of one reference's fragments.  ``fragments``: one pair
+    ``(chars, dropped)`` per fragment — ``chars`` its characters in seqout order as ``(pos, gap)``,
+    ``pos`` the 0-based position the character lands on and ``gap`` whether a D, N or P token
+    produced it; ``dropped`` whether the read's ``-`` are kept out of the counts.  An event is a
+    maximal run of gap characters next to each other in ``chars``."""
+    events = {}
+    for chars, dropped in fragments:
+        run = None   # [start, len]
+        for pos, gap in list(chars) + [(None, False)]:
+            if gap and run is not None:
+                run[1] += 1
+            elif gap:
+                run = [int(pos), 1]
+            elif run is not None:
+                e = events.setdefault((run[0], run[1]), [0, 0])
+                e[0] += 1
+                e[1] += 1 if dropped else 0
+                run = None
+    return events
+
+
+def format_deletions(events, cov, min_reads=1):
+    """The deletion lines (no header) of ``events`` = {ref name: ``gap_events``' mapping} with
+    ``cov`` = {ref name: the coverage per position}; the references in the mapping's order (the
+    header's), a reference's events by ``start``, then ``len``; those with ``reads < min_reads``
+    (>= 1) are left out."""
+    if int(min_reads) < 1:
+        raise ValueError("min_reads must be at least 1")
+    out = []
+    for ref, ev in events.items():
+        name = ref.decode("latin-1") if isinstance(ref, (bytes, bytearray)) else str(ref)
+        for (start, ln), (reads, dropped) in sorted(ev.items()):
+            if int(reads) >= int(min_reads):
+                out.append("%s\t%d\t%d\t%d\t%d\t%d\t%d\n" % (name, start + 1, start + ln, ln, reads, dropped, int(cov[ref][start])))
+    return "".join(out).encode("latin-1")
+
+
+def deletions_file(hb, prefix, offs, body):
+    """{``PREFIX.deletions.tsv``: bytes} from ``Workspace.deletions_table``'s text on the host:
+    the header and the tiles' lines as they lie (tiles are emitted reference by reference, so the
+    text is in file order; ``offs`` is not needed to cut it)."""
+    pre = prefix.encode("latin-1") if isinstance(prefix, str) else prefix
+    end = int(offs[-1]) if len(offs) else 0
+    return {pre + DEL_SUFFIX: DEL_HEADER + bytes(body[:end])}
 
 
 def table_files(hb, prefix, offs, body, header=HEADER, suffix=SUFFIX):
