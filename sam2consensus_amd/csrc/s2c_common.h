@@ -98,6 +98,40 @@ __device__ __forceinline__ void lds_poison(T *p, uint32_t bytes) {
 __device__ __forceinline__ bool op_bases(uint32_t op) { return op == S2C_OP_M || op == S2C_OP_EQ || op == S2C_OP_X; }
 __device__ __forceinline__ bool op_dash(uint32_t op) { return op == S2C_OP_D || op == S2C_OP_N || op == S2C_OP_P; }
 
+// The '-' in the seqout of a read that the maxdel rule (:210) compares with maxdel: the D / N / P
+// lengths of the tokens [o, oend) plus the '-' chars of the bases they take from SEQ (slen bases
+// from query base q0; only a piece with S2C_PF_DASH in fl has any: x = 1, p1 = 0, p0 = 1).  The one
+// copy of the rule: walk_piece drops a read's '-' from the counts by it, and the deletion table's
+// `dropped` column (s2c_dels.hip) counts the same reads.
+template <class Mem>
+__device__ __forceinline__ uint64_t piece_dashes(const Mem &m, uint32_t o, uint32_t oend, uint32_t slen, uint32_t fl, uint64_t q0) {
+    uint64_t dashes = 0, start = 0;
+    for (uint32_t j = o; j < oend; j++) {
+        const uint32_t w = m.op(j), op = w & 15u;
+        const uint64_t l = w >> 4;
+        if (op_bases(op)) {
+            uint64_t take = start < slen ? (l < slen - start ? l : slen - start) : 0;
+            if (fl & S2C_PF_DASH) {
+                uint64_t q = q0 + start;
+                while (take) {
+                    const uint64_t qw = q >> 5;
+                    const uint32_t sh = (uint32_t)(q & 31), n = (uint32_t)(take < 32 - sh ? take : 32 - sh);
+                    const uint32_t mask = (n >= 32 ? 0xFFFFFFFFu : ((1u << n) - 1u)) << sh;
+                    dashes += (uint32_t)__popc(m.x(qw) & m.p0(qw) & ~m.p1(qw) & mask);
+                    q += n;
+                    take -= n;
+                }
+            }
+            start += l;
+        } else if (op_dash(op)) {
+            dashes += l;
+        } else if (op == S2C_OP_I || op == S2C_OP_S) {
+            start += l;
+        }
+    }
+    return dashes;
+}
+
 // The token walk of the reference's parsecigar (:64-81) over one piece (start = query
 // index, k = seqout index):
 //   M / = / X   take = min(l, len(SEQ) - start) bases (SEQ truncation, :67), k += take
@@ -133,38 +167,11 @@ __device__ __forceinline__ void walk_piece(const Mem &m, const uint4 P, uint32_t
         for (uint32_t j = 0; j < 3; j++) run(o + j, 0u, 0u, S2C_RUN_EMPTY, 0ull);
         o += 3;
     }
-    bool drop = false;
-    if (maxdel_active) {   // :210
-        uint64_t dashes = 0, start = 0;
-        for (uint32_t j = o; j < oend; j++) {
-            const uint32_t w = m.op(j), op = w & 15u;
-            const uint64_t l = w >> 4;
-            if (op_bases(op)) {
-                uint64_t take = start < slen ? (l < slen - start ? l : slen - start) : 0;
-                if (fl & S2C_PF_DASH) {   // '-' chars of SEQ: x = 1, p1 = 0, p0 = 1
-                    uint64_t q = q0 + start;
-                    while (take) {
-                        const uint64_t qw = q >> 5;
-                        const uint32_t sh = (uint32_t)(q & 31), n = (uint32_t)(take < 32 - sh ? take : 32 - sh);
-                        const uint32_t mask = (n >= 32 ? 0xFFFFFFFFu : ((1u << n) - 1u)) << sh;
-                        dashes += (uint32_t)__popc(m.x(qw) & m.p0(qw) & ~m.p1(qw) & mask);
-                        q += n;
-                        take -= n;
-                    }
-                }
-                start += l;
-            } else if (op_dash(op)) {
-                dashes += l;
-            } else if (op == S2C_OP_I || op == S2C_OP_S) {
-                start += l;
-            }
-        }
-        drop = dashes > (uint64_t)maxdel;
-    }
+    const bool drop = maxdel_active && piece_dashes(m, o, oend, slen, fl, q0) > (uint64_t)maxdel;   // :210
     const uint32_t lng = (fl & S2C_PF_LONG) ? S2C_RUN_LONG : 0u;
     const uint32_t bkind = S2C_RUN_BASES | ((fl & S2C_PF_X) ? S2C_RUN_XBIT : 0u) | (drop ? S2C_RUN_DROP : 0u) | lng;
+    uint64_t start = 0;   // (declared before k: the other way round the sum for rq compiles reassociated)
     int64_t k = 0;
-    uint64_t start = 0;
     for (uint32_t j = o; j < oend; j++) {
         const uint32_t w = m.op(j), op = w & 15u;
         const uint64_t l = w >> 4;
@@ -196,7 +203,7 @@ __device__ __forceinline__ void walk_piece(const Mem &m, const uint4 P, uint32_t
     }
 }
 
-struct GlobalMem {   // walk_piece's view of the batch in HBM (k_reads, k_links_count)
+struct GlobalMem {   // walk_piece's view of the batch in HBM (k_reads, k_links_count, the long pieces of k_tile and k_tile_dense)
     const uint32_t *ops, *bq, *bx;
     __device__ __forceinline__ uint32_t op(uint32_t j) const { return ops[j]; }
     __device__ __forceinline__ uint32_t p0(uint64_t w) const { return bq[2 * w]; }
@@ -254,6 +261,11 @@ __device__ __forceinline__ uint32_t vote_mask_u32(const uint32_t (&c)[NSYM], con
 
 // char of a one-symbol mask, amb[1 << s] = "-ACGNT"[s]
 __device__ __forceinline__ uint32_t sym_char(uint32_t s) { return (uint32_t)(0x544E4743412DULL >> (8 * s)) & 0xFFu; }
+// "-ACGNT" index of one base from its plane bits: x marks '-' (p0 = 1) and N (p0 = 0), else p1 p0 = A C G T
+__device__ __forceinline__ uint32_t sym_code(uint32_t p0, uint32_t p1, uint32_t x) {
+    const uint32_t v = p1 << 1 | p0;
+    return x ? (p0 ? 0u : 4u) : (v == 3u ? 5u : v + 1u);
+}
 
 // The vote shortcut: the largest count m1 is a strict majority (so unique) and
 // m1·2^15 ≥ uq·cov with uq = ⌈tmax·2^15⌉ + 1 (per pass; 0 = off: some threshold outside

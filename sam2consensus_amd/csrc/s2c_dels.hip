@@ -19,25 +19,23 @@
 //                   slot count; a table that fills sets the overflow word.
 //   k_dels_tiles / k_dels_scatter   the slots to their tile (wtile[g >> 5]): per-tile counts, the
 //                   caller's exclusive prefix sum, a scatter into ent[].
-//   k_dels_len      one workgroup per tile, k_ins_len's scheme: a histogram of the listed entries
-//                   (reads >= min_reads, g inside the tile's block) over the tile's positions
-//                   scanned to bucket starts, the entries scattered into their position's bucket
-//                   of tmp[], each one's rank in its bucket the entries of a smaller length (they
+//   k_dels_len      one workgroup per tile: the listed entries (reads >= min_reads, g inside the
+//                   tile's block) into their position's bucket of tmp[] (s2c_text.h's
+//                   bucket_by_pos), each one's rank in its bucket the entries of a smaller length (they
 //                   are distinct by now: the quadratic term is over the lengths at one start),
 //                   the ordered entries written back over the tile's part of ent[], their line
 //                   lengths summed to lens[tile].
-//   k_dels_write    TWG ordered entries a step, a lane a line: the line lengths scanned over the
-//                   workgroup, the lines written into an LDS image that leaves with 16-byte
-//                   stores (store_text) when the step's bytes fit it, and byte by byte through
-//                   the tile's guarded range of dst when they do not (a reference name can be of
-//                   any length).
+//   k_dels_write    TWG ordered entries a step, a lane a line, through s2c_text.h's
+//                   emit_var_lines: the lines leave through an LDS image when the step's bytes
+//                   fit it, and byte by byte through the tile's guarded range of dst when they do
+//                   not (a reference name can be of any length).
+// The maxdel rule behind the DROPPED column is s2c_common.h's piece_dashes, the count walk's own.
 #include "s2c_text.h"
 
 namespace s2c {
 namespace {
 
 constexpr uint32_t DPOS = S2C_TILE_MAX;    // positions of a tile: the histogram's bins
-constexpr uint32_t LIMG = 24 * 1024 - 16;  // bytes of a step's lines that go through the LDS image
 
 struct WalkArgs {
     const uint32_t *pc, *ops, *bq, *bx;
@@ -110,41 +108,27 @@ __device__ __forceinline__ uint32_t piece_events(const WalkArgs &d, uint64_t i, 
     return n;
 }
 
-// the maxdel rule (:210) for piece i's read: more than maxdel '-' in its seqout, the D / N / P
-// lengths and the '-' chars of the bases it takes (walk_piece's first pass)
+// piece_dashes' view of a batch whose planes this file does not trust: a plane word at or past
+// n_qwords reads as zero (no '-' there)
+struct GuardedMem {
+    const uint32_t *ops, *bq, *bx;
+    uint64_t n_qwords;
+    __device__ __forceinline__ uint32_t op(uint32_t j) const { return ops[j]; }
+    __device__ __forceinline__ uint32_t p0(uint64_t w) const { return w < n_qwords ? bq[2 * w] : 0u; }
+    __device__ __forceinline__ uint32_t p1(uint64_t w) const { return w < n_qwords ? bq[2 * w + 1] : 0u; }
+    __device__ __forceinline__ uint32_t x(uint64_t w) const { return w < n_qwords ? bx[w] : 0u; }
+};
+
+// the maxdel rule (:210) for piece i's read, by the count walk's own piece_dashes: more than
+// maxdel '-' in its seqout (the tokens end at n_ops at the latest, so their indices fit 32 bits)
 __device__ __forceinline__ bool piece_dropped(const WalkArgs &d, uint64_t i) {
     const uint4 P = ((const uint4 *)d.pc)[i];
     const uint64_t oend = min((uint64_t)d.pc[4 * i + 6], d.n_ops);
-    const uint32_t slen = P.w & 0xFFFFFFu, fl = P.w >> 24;
-    const uint64_t q0 = (uint64_t)P.y * 16;
     uint64_t o;
     int64_t ka, kb;
     if (!piece_tokens(d, P, oend, o, ka, kb)) return false;
-    uint64_t dashes = 0, start = 0;
-    for (uint64_t j = o; j < oend; j++) {
-        const uint32_t w = d.ops[j], op = w & 15u;
-        const uint64_t l = w >> 4;
-        if (op_bases(op)) {
-            uint64_t take = start < slen ? (l < slen - start ? l : slen - start) : 0;
-            if (fl & S2C_PF_DASH) {   // '-' chars of SEQ: x = 1, p1 = 0, p0 = 1
-                uint64_t q = q0 + start;
-                while (take) {
-                    const uint64_t qw = q >> 5;
-                    const uint32_t sh = (uint32_t)(q & 31), n = (uint32_t)(take < 32 - sh ? take : 32 - sh);
-                    const uint32_t mask = (n >= 32 ? 0xFFFFFFFFu : ((1u << n) - 1u)) << sh;
-                    if (qw < d.n_qwords) dashes += (uint32_t)__popc(d.bx[qw] & d.bq[2 * qw] & ~d.bq[2 * qw + 1] & mask);
-                    q += n;
-                    take -= n;
-                }
-            }
-            start += l;
-        } else if (op_dash(op)) {
-            dashes += l;
-        } else if (op == S2C_OP_I || op == S2C_OP_S) {
-            start += l;
-        }
-    }
-    return dashes > (uint64_t)d.maxdel;
+    return piece_dashes(GuardedMem{d.ops, d.bq, d.bx, d.n_qwords}, (uint32_t)o, (uint32_t)oend, P.w & 0xFFFFFFu, P.w >> 24,
+                        (uint64_t)P.y * 16) > (uint64_t)d.maxdel;
 }
 
 // an event clamped to padded_len: false when nothing of it is left
@@ -290,13 +274,6 @@ __device__ __forceinline__ Line line_of(const DelArgs &d, const Tile &T, const u
     return L;
 }
 
-// the LDS image as put_line's destination: every line of a step lies inside it
-struct Img {
-    uint8_t *b;
-    __device__ __forceinline__ void put(uint64_t o, uint32_t ch) const { b[o] = (uint8_t)ch; }
-    __device__ __forceinline__ uint8_t &operator[](uint64_t o) const { return b[o]; }
-};
-
 // the line at o[at, at + L.len): the name forwards, the numbers backwards from the line's end
 template <typename Dst>
 __device__ __forceinline__ void put_line(const Dst &o, uint64_t at, const Tile &T, const Line &L) {
@@ -315,12 +292,6 @@ __device__ __forceinline__ void put_line(const Dst &o, uint64_t at, const Tile &
     o.put(--e, '\t');
     e = put64(o, e, L.start);
     o.put(--e, '\t');
-}
-
-// Workgroup barrier that also orders the workgroup's global (scratch) stores before its loads
-__device__ __forceinline__ void wg_sync() {
-    __threadfence_block();
-    __syncthreads();
 }
 
 // lens[t] = bytes of tile t's lines; its listed entries in order at the front of its part of ent[], tn[t] of them
@@ -344,48 +315,13 @@ __global__ __launch_bounds__(TWG) void k_dels_len(const DelArgs d, int64_t *__re
             continue;
         }
         uint4 *ent = d.ent + T.t0, *tmp = d.tmp + T.t0;
-        // (1) listed entries per position
-        for (uint32_t p = tid; p <= DPOS; p += TWG) start[p] = 0u;
-        for (uint32_t p = tid; p < DPOS; p += TWG) cursor[p] = 0u;
-        lds_sync();
-        for (uint32_t e = tid; e < T.cap; e += TWG) {
-            const uint4 v = ent[e];
-            if (listed(d, T, v)) atomicAdd(&start[(uint32_t)((int64_t)v.x - T.B.a)], 1u);
-        }
-        lds_sync();
-        // (2) bucket starts: each lane its 8 bins, the lanes' sums scanned over the workgroup
-        {
-            constexpr uint32_t PER = DPOS / TWG;
-            uint32_t c[PER], sum = 0;
-#pragma unroll
-            for (uint32_t k = 0; k < PER; k++) {
-                c[k] = start[PER * tid + k];
-                sum += c[k];
+        // (1)-(3) the listed entries (n ≤ cap) into their position's bucket of tmp[]
+        const uint32_t n = bucket_by_pos<DPOS>(start, cursor, wsum, total, tmp, tid, lane, wv, [&](auto f) {
+            for (uint32_t e = tid; e < T.cap; e += TWG) {
+                const uint4 v = ent[e];
+                if (listed(d, T, v)) f((uint32_t)((int64_t)v.x - T.B.a), v);
             }
-            const uint32_t inc = wave_scan(sum, lane);
-            if (lane == 63u) wsum[wv] = inc;
-            lds_sync();
-            uint32_t run = inc - sum;
-#pragma unroll
-            for (uint32_t w = 0; w < TWG / 64; w++) run += w < wv ? (uint32_t)wsum[w] : 0u;
-#pragma unroll
-            for (uint32_t k = 0; k < PER; k++) {
-                start[PER * tid + k] = run;
-                run += c[k];
-            }
-            if (tid == TWG - 1) start[DPOS] = total = run;
-            lds_sync();
-        }
-        const uint32_t n = total;   // listed entries (≤ cap)
-        // (3) scatter into the buckets of tmp[] (the order inside a bucket is the atomics', and
-        // nothing below depends on it)
-        for (uint32_t e = tid; e < T.cap; e += TWG) {
-            const uint4 v = ent[e];
-            if (listed(d, T, v)) {
-                const uint32_t pos = (uint32_t)((int64_t)v.x - T.B.a);
-                tmp[start[pos] + atomicAdd(&cursor[pos], 1u)] = v;
-            }
-        }
+        });
         wg_sync();   // (ent[] is read no more: the ordered entries go back over it)
         // (4) every entry's place: its bucket's start plus the entries of a smaller length
         for (uint32_t i = tid; i < n; i += TWG) {
@@ -432,29 +368,7 @@ __global__ __launch_bounds__(TWG) void k_dels_write(const DelArgs d, const int64
                 const uint4 v = ent[s0 + tid];
                 if (listed(d, T, v)) L = line_of(d, T, v);
             }
-            const uint32_t inc = wave_scan(L.len, lane);
-            if (lane == 63u) wtot[wv] = inc;
-            lds_sync();
-            uint64_t below = 0, tot = 0;   // (a name can be long: 64-bit sums)
-#pragma unroll
-            for (uint32_t w = 0; w < TWG / 64; w++) {
-                const uint32_t tw = wtot[w];
-                below += w < wv ? tw : 0u;
-                tot += tw;
-            }
-            const uint64_t at = below + (inc - L.len);
-            if (tot <= LIMG) {   // (the same in every lane)
-                uint8_t *dd = o.d + run;
-                const uint32_t sh = (uint32_t)((uintptr_t)dd & 15u);
-                if (L.len) put_line(Img{buf}, sh + at, T, L);
-                lds_sync();
-                // (offs that do not match the lengths: the text is cut at the tile's range)
-                const uint64_t left = run < o.cap ? o.cap - run : 0ull;
-                if (left) store_text(buf, dd, sh, (uint32_t)min(tot, left), tid);
-            } else if (L.len) {
-                put_line(o, run + at, T, L);
-            }
-            run += tot;
+            run += emit_var_lines<LIMG>(buf, wtot, o, run, L.len, tid, lane, wv, [&](const auto &to, uint64_t at) { put_line(to, at, T, L); });
         }
     }
 }
@@ -467,9 +381,6 @@ int walk_args(WalkArgs &a, const uint32_t *pc, const uint32_t *ops, int64_t n_pi
     a.n = (uint32_t)n_pieces; a.n_ops = (uint64_t)n_ops; a.padded_len = (uint64_t)padded_len;
     return S2C_OK;
 }
-inline unsigned walk_grid(int64_t n) { return (unsigned)std::min<int64_t>((n + TWG - 1) / TWG, 8 * 256 * 4); }
-// the two walks: 8 workgroups per CU, grid-strided
-inline unsigned piece_grid(int64_t n) { return (unsigned)std::min<int64_t>((n + TWG - 1) / TWG, 8 * 256); }
 
 int bucket_sizes(int64_t n_slots, int64_t n_words, int64_t n_tiles) {
     if (n_slots < 0 || n_slots > (1ll << 40) || n_words < 0 || n_tiles < 0 || n_tiles > 0xFFFFFFFFll)

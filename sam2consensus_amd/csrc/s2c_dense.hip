@@ -173,15 +173,6 @@ __device__ __forceinline__ void walk_window(const uint32_t *opl, uint32_t ob, co
     }
 }
 
-// walk_piece's view of the batch in HBM (the tile's long pieces)
-struct DenseMem {
-    const uint32_t *ops, *bq, *bx;
-    __device__ __forceinline__ uint32_t op(uint32_t j) const { return ops[j]; }
-    __device__ __forceinline__ uint32_t p0(uint64_t w) const { return bq[2 * w]; }
-    __device__ __forceinline__ uint32_t p1(uint64_t w) const { return bq[2 * w + 1]; }
-    __device__ __forceinline__ uint32_t x(uint64_t w) const { return bx[w]; }
-};
-
 // A rare piece's record (drare; s2c.h S2C_DPC_WORDS) decoded: rs = its start relative to the
 // tile's first word + REC_BIAS, q = query base of SEQ[0] in the window's planes, its op slots
 // [j, j + nops) in the window, len(SEQ), flags (x: word 0, y: word 1)
@@ -806,7 +797,7 @@ __device__ __forceinline__ void dense_tile(const DenseArgs &d, const Win &v, con
             const uint32_t k = d.lp[v.lp0 + j];
             const uint4 P = ((const uint4 *)d.pc)[k];
             const uint32_t oend = d.pc[4 * (size_t)k + 6];   // next piece's op offset
-            walk_piece(DenseMem{d.ops, d.bq, d.bx}, P, oend, mda, d.maxdel,
+            walk_piece(GlobalMem{d.ops, d.bq, d.bx}, P, oend, mda, d.maxdel,
                        [&](uint32_t, uint32_t gp, uint32_t l, uint32_t kind, uint64_t q) {
                            const uint32_t kd = kind & 3u;
                            if (kd != S2C_RUN_BASES && kd != S2C_RUN_DASH) return;

@@ -11,18 +11,18 @@
 // Hash slot order and the arrival order of the atomics must not show in the bytes, so every
 // tile's entries are ordered by (position; reads, falling; length; motif in -ACGNT order) — a
 // total order.  One workgroup per tile, grid-strided; k_ins_len, for its tile:
-//   count    the valid entries per position into an LDS histogram (2,048 bins), scanned to
-//            bucket starts;
-//   scatter  every entry into its position's bucket of ent[] (HBM scratch; the order inside a
-//            bucket is the atomics', and nothing below depends on it);
+//   bucket   the valid entries of both sources into their position's bucket of ent[] (HBM
+//            scratch), by s2c_text.h's bucket_by_pos: an LDS histogram (2,048 bins), scanned to
+//            bucket starts, a scatter (the order inside a bucket is the atomics', and nothing
+//            below depends on it);
 //   group    every long event counts the events of its bucket with its length and content
 //            (compared through the planes, 32 bases a step): the one at the lowest slot keeps
 //            the count as its reads, the others get 0 and are dead from here on;
 //   rank     every live entry (reads >= min_reads) counts the live entries of its bucket that
 //            come before it: its place in ord[] is the bucket's start plus that rank (the
 //            dead entries' places stay holes behind the live ones);
-//   scan     line lengths over ord[] in order, their exclusive 64-bit prefix sum kept per
-//            place, the total to lens[tile].
+//   scan     line lengths over ord[] in order, their exclusive 64-bit prefix sum (wg_scan) kept
+//            per place, the total to lens[tile].
 // No step holds entries in LDS, so no count of entries per tile is special: the work is
 // Σ over positions of (entries at the position)², a handful per position in real data.
 // k_ins_write walks ord[]: a lane per place writes its line's numbers and, for a short motif,
@@ -82,15 +82,11 @@ __device__ __forceinline__ bool long_ok(const uint4 &v, uint32_t npos, uint64_t 
     return v.x < npos && v.y >= 1u && v.y < ILEN_END && q < (1ull << 48) && q + v.y <= 32ull * n_qwords;
 }
 
-// "-ACGNT" index from the plane bits of one base (add_event's mapping)
-__device__ __forceinline__ uint32_t code_of(uint32_t p0, uint32_t p1, uint32_t x) {
-    const uint32_t v = p1 << 1 | p0;
-    return x ? (p0 ? 0u : 4u) : (v == 3u ? 5u : v + 1u);
-}
+// "-ACGNT" index of query base q (add_event's mapping: sym_code)
 __device__ __forceinline__ uint32_t plane_code(const InsArgs &d, uint64_t q) {
     const uint64_t w = q >> 5;
     const uint32_t sh = (uint32_t)(q & 31);
-    return code_of((d.bq[2 * w] >> sh) & 1u, (d.bq[2 * w + 1] >> sh) & 1u, (d.bx[w] >> sh) & 1u);
+    return sym_code((d.bq[2 * w] >> sh) & 1u, (d.bq[2 * w + 1] >> sh) & 1u, (d.bx[w] >> sh) & 1u);
 }
 // symbol c of an entry's motif
 __device__ __forceinline__ uint32_t e_sym(const InsArgs &d, const uint4 &e, uint32_t c) {
@@ -123,8 +119,8 @@ __device__ __forceinline__ int cmp_motif(const InsArgs &d, const uint4 &A, const
             const uint32_t df = (a.p0 ^ b.p0) | (a.p1 ^ b.p1) | (a.x ^ b.x);
             if (df) {
                 const uint32_t k = (uint32_t)__builtin_ctz(df);
-                const uint32_t ca = code_of((a.p0 >> k) & 1u, (a.p1 >> k) & 1u, (a.x >> k) & 1u);
-                const uint32_t cb = code_of((b.p0 >> k) & 1u, (b.p1 >> k) & 1u, (b.x >> k) & 1u);
+                const uint32_t ca = sym_code((a.p0 >> k) & 1u, (a.p1 >> k) & 1u, (a.x >> k) & 1u);
+                const uint32_t cb = sym_code((b.p0 >> k) & 1u, (b.p1 >> k) & 1u, (b.x >> k) & 1u);
                 return ca < cb ? -1 : 1;
             }
         }
@@ -153,12 +149,6 @@ __device__ __forceinline__ bool before(const InsArgs &d, const uint4 &J, uint32_
     return j < i;   // (equal lines: duplicate keys of a hand-built table)
 }
 
-// Workgroup barrier that also orders the workgroup's global (scratch) stores before its loads
-__device__ __forceinline__ void wg_sync() {
-    __threadfence_block();
-    __syncthreads();
-}
-
 // lens[t] = bytes of tile t's lines; ent[] and ord[] of the tile for k_ins_write
 __global__ __launch_bounds__(TWG) void k_ins_len(const InsArgs d, int64_t *__restrict__ lens) {
     __shared__ uint32_t start[IPOS + 1];   // entries per position, then the buckets' starts
@@ -184,56 +174,18 @@ __global__ __launch_bounds__(TWG) void k_ins_len(const InsArgs d, int64_t *__res
         const uint4 *lg = (const uint4 *)d.ilong + R.loff;
         uint4 *ent = d.ent + R.base, *ord = d.ord + R.base;
         const uint32_t cap = (uint32_t)min(R.cap, (uint64_t)0xFFFFFFFEu);
-        // (1) entries per position
-        for (uint32_t p = tid; p <= IPOS; p += TWG) start[p] = 0u;
-        for (uint32_t p = tid; p < IPOS; p += TWG) cursor[p] = 0u;
-        lds_sync();
-        for (uint32_t e = tid; e < R.bcap; e += TWG) {
-            const uint4 v = bk[e];
-            if (short_ok(v, npos)) atomicAdd(&start[v.x & 0x7FFu], 1u);
-        }
-        for (uint32_t e = tid; e < nl; e += TWG) {
-            const uint4 v = lg[e];
-            if (long_ok(v, npos, d.n_qwords)) atomicAdd(&start[v.x], 1u);
-        }
-        lds_sync();
-        // (2) bucket starts: each lane its 8 bins, the lanes' sums scanned over the workgroup
-        {
-            constexpr uint32_t PER = IPOS / TWG;
-            uint32_t c[PER], sum = 0;
-#pragma unroll
-            for (uint32_t k = 0; k < PER; k++) {
-                c[k] = start[PER * tid + k];
-                sum += c[k];
+        // (1)-(3) the valid entries (n ≤ cap) of both sources into their position's bucket of
+        // ent[]; every place of ord[] a hole
+        const uint32_t n = bucket_by_pos<IPOS>(start, cursor, wsum, total, ent, tid, lane, wv, [&](auto f) {
+            for (uint32_t e = tid; e < R.bcap; e += TWG) {
+                const uint4 v = bk[e];
+                if (short_ok(v, npos)) f(v.x & 0x7FFu, make_uint4(v.x, v.y, v.z, (v.x >> 11) & 31u));
             }
-            const uint32_t inc = wave_scan(sum, lane);
-            if (lane == 63u) wsum[wv] = inc;
-            lds_sync();
-            uint32_t run = inc - sum;
-#pragma unroll
-            for (uint32_t w = 0; w < TWG / 64; w++) run += w < wv ? (uint32_t)wsum[w] : 0u;
-#pragma unroll
-            for (uint32_t k = 0; k < PER; k++) {
-                start[PER * tid + k] = run;
-                run += c[k];
+            for (uint32_t e = tid; e < nl; e += TWG) {
+                const uint4 v = lg[e];
+                if (long_ok(v, npos, d.n_qwords)) f(v.x, make_uint4(v.z, (v.w & 0xFFFFu) | (v.x << 16), 1u, v.y | (1u << 31)));
             }
-            if (tid == TWG - 1) start[IPOS] = total = run;
-            lds_sync();
-        }
-        const uint32_t n = total;   // valid entries (≤ cap)
-        // (3) scatter into the buckets; every place of ord[] a hole
-        for (uint32_t e = tid; e < R.bcap; e += TWG) {
-            const uint4 v = bk[e];
-            if (short_ok(v, npos)) {
-                const uint32_t pos = v.x & 0x7FFu;
-                ent[start[pos] + atomicAdd(&cursor[pos], 1u)] = make_uint4(v.x, v.y, v.z, (v.x >> 11) & 31u);
-            }
-        }
-        for (uint32_t e = tid; e < nl; e += TWG) {
-            const uint4 v = lg[e];
-            if (long_ok(v, npos, d.n_qwords))
-                ent[start[v.x] + atomicAdd(&cursor[v.x], 1u)] = make_uint4(v.z, (v.w & 0xFFFFu) | (v.x << 16), 1u, v.y | (1u << 31));
-        }
+        });
         for (uint32_t s = tid; s < cap; s += TWG) ord[s] = make_uint4(HOLE, 0u, 0u, 0u);
         wg_sync();
         // (4) equal long events of a bucket → one entry with their number as its reads
@@ -278,17 +230,10 @@ __global__ __launch_bounds__(TWG) void k_ins_len(const InsArgs d, int64_t *__res
                 len = ndig64((uint64_t)B.p0 + pos) + ndig64(cov_at(d.counts, (uint64_t)d.padded_len, (uint64_t)B.a + pos)) + ndig32(E.z) +
                       ndig32(e_len(E)) + e_len(E) + 5u;   // (< 2^24 + 64: a wave's sum fits 32 bits)
             }
-            const uint32_t inc = wave_scan(len, lane);
-            if (lane == 63u) wsum[wv] = inc;
-            lds_sync();
-            uint64_t below = 0, tot = 0;
-#pragma unroll
-            for (uint32_t w = 0; w < TWG / 64; w++) {
-                below += w < wv ? wsum[w] : 0ull;
-                tot += wsum[w];
-            }
+            uint64_t tot;
+            const uint64_t end = wg_scan(len, wsum, lane, wv, tot);
             if (i != HOLE) {
-                const uint64_t off = run + below + (inc - len);
+                const uint64_t off = run + end - len;
                 ord[s] = make_uint4(i, (uint32_t)off, (uint32_t)(off >> 32), len);
             }
             run += tot;

@@ -27,10 +27,10 @@
 //                  site reads its row of 36 counts; a listed pair looks its second site up in
 //                  the mask (a fragment spans the two, so it is near).  Lines run to 542 bytes:
 //                  an LDS image of TWG of them would leave one workgroup a CU.  The write pass
-//                  scans the step's line lengths as emit_lines does and, when they sum to at most
-//                  LIMG bytes (44 bytes a line on C5: nearly always), writes them into an image
-//                  of that size and stores it with store_text; a longer step stores its bytes
-//                  singly through the block's guarded range (Out).
+//                  hands a step's lines to s2c_text.h's emit_var_lines: when they sum to at most
+//                  LIMG bytes (44 bytes a line on C5: nearly always) they go through an image of
+//                  that size and store_text; a longer step stores its bytes singly through the
+//                  block's guarded range (Out).  put_line writes to either.
 #include "s2c_text.h"
 
 namespace s2c {
@@ -43,14 +43,6 @@ constexpr uint32_t HSTEPS = 4;             // steps of TWG pieces between two fl
 constexpr uint32_t HEMPTY = 0xFFFFFFFFu;
 constexpr uint32_t NO_RANK = 0xFFFFFFFEu;  // (+ 1 is no rank either: ranks stay below n_sites < 2^32)
 constexpr uint64_t SYMS = 0x544E4743412Dull;   // "-ACGNT", symbol s in byte s
-constexpr uint32_t LIMG = 24 * 1024 - 16;  // bytes of a step's lines that go through the LDS image (5 workgroups a CU)
-
-// the LDS image as put_line's destination: every line of a step lies inside [sh, sh + its total)
-struct Img {
-    uint8_t *b;
-    __device__ __forceinline__ void put(uint64_t o, uint32_t ch) const { b[o] = (uint8_t)ch; }
-    __device__ __forceinline__ uint8_t &operator[](uint64_t o) const { return b[o]; }
-};
 
 __global__ __launch_bounds__(TWG) void k_links_pop(const uint64_t *__restrict__ mask, uint64_t n_words, uint32_t *__restrict__ pop) {
     for (uint64_t w = (uint64_t)blockIdx.x * TWG + threadIdx.x; w < n_words; w += (uint64_t)gridDim.x * TWG)
@@ -108,9 +100,9 @@ __device__ __forceinline__ void piece_links(const CountArgs &d, uint32_t *hkey, 
                                const uint64_t qq = q + (p - g), qw = qq >> 5;
                                const uint32_t sh = (uint32_t)(qq & 31u);
                                if (qw >= d.n_qwords) continue;
-                               const uint32_t p0 = (d.bq[2 * qw] >> sh) & 1u, v = ((d.bq[2 * qw + 1] >> sh) & 1u) << 1 | p0;
+                               const uint32_t p0 = (d.bq[2 * qw] >> sh) & 1u, p1 = (d.bq[2 * qw + 1] >> sh) & 1u;
                                const uint32_t x = (kind & S2C_RUN_XBIT) ? (d.bx[qw] >> sh) & 1u : 0u;
-                               sym = x ? (p0 ? 0u : 4u) : (v == 3u ? 5u : v + 1u);
+                               sym = sym_code(p0, p1, x);
                                if (sym == 0u && (kind & S2C_RUN_DROP)) continue;   // (:210: this '-' is not counted)
                            }
                            if ((uint64_t)r >= d.n_sites) continue;
@@ -312,29 +304,7 @@ __global__ __launch_bounds__(TWG) void k_links_write(const LinkArgs d, const int
             lds_sync();   // (the entries are in; wtot and buf are no longer read)
             Line L{};
             if (tid < cnt) L = line_of(d, B, queue[(qh + tid) & (QCAP - 1u)]);
-            const uint32_t inc = wave_scan(L.len, lane);
-            if (lane == 63u) wtot[wv] = inc;
-            lds_sync();
-            uint32_t below = 0, tot = 0;
-#pragma unroll
-            for (uint32_t w = 0; w < TWG / 64; w++) {
-                const uint32_t t = wtot[w];
-                below += w < wv ? t : 0u;
-                tot += t;
-            }
-            const uint32_t at = below + (inc - L.len);
-            if (tot <= LIMG) {   // (the same in every lane)
-                uint8_t *dd = o.d + run;
-                const uint32_t sh = (uint32_t)((uintptr_t)dd & 15u);
-                if (L.len) put_line(Img{buf}, sh + at, L);
-                lds_sync();
-                // (offs that do not match the lengths: the text is cut at the block's range)
-                const uint64_t left = run < o.cap ? o.cap - run : 0ull;
-                if (left) store_text(buf, dd, sh, (uint32_t)min((uint64_t)tot, left), tid);
-            } else if (L.len) {
-                put_line(o, run + at, L);
-            }
-            run += tot;
+            run += emit_var_lines<LIMG>(buf, wtot, o, run, L.len, tid, lane, wv, [&](const auto &to, uint64_t at) { put_line(to, at, L); });
         });
     }
 }
@@ -366,8 +336,7 @@ extern "C" int s2c_links_pop(const uint64_t *mask, int64_t padded_len, uint32_t 
     if (padded_len == 0) return S2C_OK;
     if (!mask || !pop) return s2c_set_error(S2C_ERR_ARG, "NULL link table buffer");
     const int64_t n_words = (padded_len + 63) / 64;
-    const unsigned grid = (unsigned)std::min<int64_t>((n_words + TWG - 1) / TWG, 8 * 256 * 4);
-    k_links_pop<<<grid, TWG, 0, (hipStream_t)stream>>>(mask, (uint64_t)n_words, pop);
+    k_links_pop<<<walk_grid(n_words), TWG, 0, (hipStream_t)stream>>>(mask, (uint64_t)n_words, pop);
     return launched("k_links_pop");
 }
 
@@ -385,8 +354,8 @@ extern "C" int s2c_links_count(const uint32_t *pc, const uint32_t *ops, const ui
     a.n = (uint32_t)n_pieces;
     a.maxdel_active = maxdel_active ? 1u : 0u;
     a.maxdel = maxdel < 0 ? 0u : (uint32_t)maxdel;
-    // 8 workgroups per CU, each a contiguous stretch of whole TWG-piece steps
-    const int64_t steps = (n_pieces + TWG - 1) / TWG, grid0 = std::min<int64_t>(steps, 8 * 256);
+    // piece_grid's workgroups, each a contiguous stretch of whole TWG-piece steps
+    const int64_t steps = (n_pieces + TWG - 1) / TWG, grid0 = piece_grid(n_pieces);
     const int64_t per = (steps + grid0 - 1) / grid0 * TWG;
     a.per = (uint32_t)per;
     k_links_count<<<(unsigned)((n_pieces + per - 1) / per), TWG, 0, (hipStream_t)stream>>>(a);

@@ -70,8 +70,7 @@ __device__ void add_event(const ReadsArgs &d, uint64_t gkey, uint64_t q, uint32_
         for (uint32_t c = 0; c < len; c++) {
             const uint32_t p0 = (uint32_t)(c01[0] >> (sh + c)) & 1u, p1 = (uint32_t)(c01[1] >> (sh + c)) & 1u,
                            x = (uint32_t)(c01[2] >> (sh + c)) & 1u;
-            const uint32_t code = x ? (p0 ? 0u : 4u) : ((p1 << 1 | p0) == 3u ? 5u : (p1 << 1 | p0) + 1u);
-            key |= (uint64_t)code << (16 + 3 * c);
+            key |= (uint64_t)sym_code(p0, p1, x) << (16 + 3 * c);
         }
         const uint32_t boff = tw1.x, bcap = tw1.y;
         uint32_t s = (uint32_t)mix64(key) & (bcap - 1u);

@@ -1,6 +1,6 @@
 // s2c_text.h — the scheme of the kernels that write tables as text (s2c_table.hip, s2c_sites.hip,
-// s2c_runs.hip, s2c_ins.hip, s2c_links.hip); each of those files keeps its line's format and what
-// it selects.
+// s2c_runs.hip, s2c_ins.hip, s2c_links.hip, s2c_dels.hip); each of those files keeps its line's
+// format and what it selects.
 //
 // Lines have no fixed width, so a table takes two launches over its blocks {a, b, p0}, one
 // workgroup per block, grid-strided: a length pass (block_total: lens[i] = bytes of block i's
@@ -12,9 +12,14 @@
 // destination's misalignment, so LDS reads and global stores are both 16-byte aligned; head and
 // tail bytes go out singly.  A sparse table picks its lines by a mask of one bit per position
 // that a mark kernel left, and walk_mask queues a block's set bits for the two passes.
+// The event tables (insertions, links, deletions) have lines without a useful width bound and
+// entries that arrive in no order.  Their write step is emit_var_lines: the same scan, then the
+// LDS image (Img) and store_text when the step's bytes fit it, and the guarded byte writer (Out)
+// when they do not.  Their entries are ordered by bucket_by_pos, a counting sort over a tile's
+// positions in LDS.  Both scan with wg_scan, the workgroup's prefix sum.
 // Also here: the decimal digit code, one position's row and its counts line, the blocks with
-// their guards (with their reference's range: RBlk), and the guarded byte writer (Out) of the
-// kernels whose lines are too long for the LDS image.
+// their guards (with their reference's range: RBlk), the barrier that orders a workgroup's
+// scratch in HBM (wg_sync), and the launch grids.
 #pragma once
 #include "s2c_common.h"
 
@@ -38,6 +43,26 @@ __device__ __forceinline__ uint32_t wave_scan(uint32_t x, uint32_t lane) {
     const uint32_t r0 = __shfl(inc, 15), r1 = __shfl(inc, 31), r2 = __shfl(inc, 47);
     inc += (lane >= 16u ? r0 : 0u) + (lane >= 32u ? r1 : 0u) + (lane >= 48u ? r2 : 0u);
     return inc;
+}
+// Inclusive prefix sum over the workgroup, in S (a wave's own sum fits 32 bits), and the
+// workgroup's total: the wave's scan, lane 63 stores the wave's total, a barrier, the totals of
+// the waves below.  wtot: TWG / 64 words of LDS that no lane still reads when the call starts; a
+// barrier of the caller's stands between this call's reads and the next write of them.
+// (emit_lines and k_table_write keep their own lines: DESIGN §4.4a)
+template <typename S, typename W>
+__device__ __forceinline__ S wg_scan(uint32_t x, W *wtot, uint32_t lane, uint32_t wv, S &tot) {
+    const uint32_t inc = wave_scan(x, lane);
+    if (lane == 63u) wtot[wv] = inc;
+    lds_sync();
+    S below = 0;
+    tot = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < TWG / 64; w++) {
+        const S t = (S)wtot[w];
+        below += w < wv ? t : (S)0;
+        tot += t;
+    }
+    return below + inc;
 }
 
 __device__ __forceinline__ uint32_t ndig32(uint32_t x) {
@@ -144,8 +169,9 @@ __device__ __forceinline__ RBlk load_rblk(const int64_t *__restrict__ blocks, co
     return RBlk{blocks[3 * i], blocks[3 * i + 1], blocks[3 * i + 2], refs[2 * i], refs[2 * i + 1]};
 }
 
-// A block's range of dst for a writer that stores byte by byte (s2c_ins.hip, s2c_links.hip): no byte is stored outside [0, cap).  o[k] = ch is put(k, ch), so
-// put32 / put64 write their digits through it.
+// A block's range of dst for a writer that stores byte by byte (k_ins_write; emit_var_lines'
+// long steps): no byte is stored outside [0, cap).  o[k] = ch is put(k, ch), so put32 / put64
+// write their digits through it.
 struct Out {
     uint8_t *d;
     uint64_t cap;
@@ -158,6 +184,12 @@ struct Out {
         __device__ __forceinline__ void operator=(uint8_t ch) const { out.put(o, ch); }
     };
     __device__ __forceinline__ Byte operator[](uint64_t o) const { return Byte{*this, o}; }
+};
+// the LDS image behind the same two calls: every line of a step lies inside it (emit_var_lines)
+struct Img {
+    uint8_t *b;
+    __device__ __forceinline__ void put(uint64_t o, uint32_t ch) const { b[o] = (uint8_t)ch; }
+    __device__ __forceinline__ uint8_t &operator[](uint64_t o) const { return b[o]; }
 };
 
 // buf[sh, sh + tot) → d[0, tot), sh = d's offset inside its 16-byte word: 16-byte stores (LDS
@@ -207,6 +239,33 @@ __device__ __forceinline__ uint32_t emit_lines(uint8_t (&buf)[BUF], uint32_t *wt
 }
 constexpr int text_buf(int line) { return TWG * line + 16; }   // + the destination's misalignment (< 16)
 
+// The write side of a table whose lines have no useful width bound (k_links_write,
+// k_dels_write: a reference name can have any length, so the sums are 64-bit).  Lane tid has a
+// line of len bytes (0: none); put(o, at) writes it at o[at, at + len), o an Img or an Out.  The
+// step's lines go, in lane order, to out.d[run, ...): through the LDS image buf and store_text
+// when they sum to at most IMG bytes, byte by byte through out's guard when they do not; cut at
+// out.cap either way.  Returns the step's bytes (the same in every lane).  wtot and buf: nobody
+// still reads them when the call starts (the caller's step starts with a barrier).
+constexpr uint32_t LIMG = 24 * 1024 - 16;   // the event tables' image: five workgroups a CU with the links' queue
+template <uint32_t IMG, typename Put>
+__device__ __forceinline__ uint64_t emit_var_lines(uint8_t (&buf)[IMG + 16], uint32_t *wtot, const Out &out, uint64_t run, uint32_t len,
+                                                   uint32_t tid, uint32_t lane, uint32_t wv, Put put) {
+    uint64_t tot;
+    const uint64_t at = wg_scan(len, wtot, lane, wv, tot) - len;
+    if (tot <= IMG) {   // (the same in every lane)
+        uint8_t *d = out.d + run;
+        const uint32_t sh = (uint32_t)((uintptr_t)d & 15u);
+        if (len) put(Img{buf}, sh + at);
+        lds_sync();
+        // (offs that do not match the lengths: the text is cut at the block's range)
+        const uint64_t left = run < out.cap ? out.cap - run : 0ull;
+        if (left) store_text(buf, d, sh, (uint32_t)min(tot, left), tid);
+    } else if (len) {
+        put(out, run + at);
+    }
+    return tot;
+}
+
 // The length side: out[0] = Σ of sum over the workgroup (wsum: a word of LDS per wave).
 __device__ __forceinline__ void block_total(uint64_t sum, uint64_t *wsum, uint32_t tid, int64_t *out) {
     sum = wave_sum(sum);
@@ -218,6 +277,50 @@ __device__ __forceinline__ void block_total(uint64_t sum, uint64_t *wsum, uint32
         *out = (int64_t)t;
     }
     lds_sync();   // (wsum is written again for the next block)
+}
+
+// Workgroup barrier that also orders the workgroup's global (scratch) stores before its loads
+__device__ __forceinline__ void wg_sync() {
+    __threadfence_block();
+    __syncthreads();
+}
+
+// A tile's entries ordered by position (k_ins_len, k_dels_len): a counting sort over the tile's
+// NPOS positions in LDS.  each(f) is the caller's loop over its sources, grid-strided over the
+// workgroup; it calls f(pos, entry) for every valid entry, pos < NPOS, and is run twice: a
+// histogram of the entries per position, then — the histogram scanned to the buckets' starts,
+// each lane its NPOS / TWG bins — a scatter of every entry into its position's bucket of out[].
+// Leaves start[p] the first place of position p's bucket (start[NPOS] = the entries, which is
+// returned; total is the word of LDS they go through) and the order inside a bucket the
+// atomics', on which nothing may depend.  The caller's wg_sync stands between the scatter and
+// its reads of out[], and another before the next call (start, cursor and total are written again).
+template <uint32_t NPOS, typename Each>
+__device__ __forceinline__ uint32_t bucket_by_pos(uint32_t (&start)[NPOS + 1], uint32_t (&cursor)[NPOS], uint64_t *wsum, uint32_t &total,
+                                                  uint4 *out, uint32_t tid, uint32_t lane, uint32_t wv, Each each) {
+    constexpr uint32_t PER = NPOS / TWG;
+    static_assert(PER * TWG == NPOS, "every lane scans the same number of bins");
+    for (uint32_t p = tid; p <= NPOS; p += TWG) start[p] = 0u;
+    for (uint32_t p = tid; p < NPOS; p += TWG) cursor[p] = 0u;
+    lds_sync();
+    each([&](uint32_t pos, const uint4 &) { atomicAdd(&start[pos], 1u); });
+    lds_sync();
+    uint32_t c[PER], sum = 0, all;
+#pragma unroll
+    for (uint32_t k = 0; k < PER; k++) {
+        c[k] = start[PER * tid + k];
+        sum += c[k];
+    }
+    uint32_t at = wg_scan(sum, wsum, lane, wv, all) - sum;
+#pragma unroll
+    for (uint32_t k = 0; k < PER; k++) {
+        start[PER * tid + k] = at;
+        at += c[k];
+    }
+    if (tid == TWG - 1) start[NPOS] = total = at;
+    lds_sync();
+    const uint32_t n = total;
+    each([&](uint32_t pos, const uint4 &e) { out[start[pos] + atomicAdd(&cursor[pos], 1u)] = e; });
+    return n;
 }
 
 constexpr uint32_t MWORDS = TWG / 64;      // mask words per step of the walk: one per wave
@@ -274,6 +377,10 @@ __device__ __forceinline__ void walk_mask(const uint64_t *__restrict__ mask, con
 
 // the grid of a table's len and write kernels over n blocks: 8 workgroups per CU
 inline unsigned text_grid(int64_t n) { return (unsigned)std::min<int64_t>(n, 8 * 256 * 4); }
+// the grids of the grid-strided kernels with a lane per item over n items (mask words, hash
+// slots: walk_grid) and of those whose lane walks a piece's tokens (piece_grid: 8 workgroups per CU)
+inline unsigned walk_grid(int64_t n) { return (unsigned)std::min<int64_t>((n + TWG - 1) / TWG, 8 * 256 * 4); }
+inline unsigned piece_grid(int64_t n) { return (unsigned)std::min<int64_t>((n + TWG - 1) / TWG, 8 * 256); }
 
 // a launcher's last line: S2C_OK, or the launch's error as "<kernel>: <what HIP says>"
 inline int launched(const char *kernel) {

@@ -127,21 +127,11 @@ __device__ __forceinline__ TileRec tile_rec(const uint32_t *tiles, uint32_t t) {
             uni(v2.x), uni(v2.y), uni(v2.z), uni(v2.w), uni(v3.x)};
 }
 
-// walk_piece's view of the batch in HBM (a dense tile's long pieces in counts-only modes)
-struct TileMem {
-    const uint32_t *ops, *bq, *bx;
-    __device__ __forceinline__ uint32_t op(uint32_t j) const { return ops[j]; }
-    __device__ __forceinline__ uint32_t p0(uint64_t w) const { return bq[2 * w]; }
-    __device__ __forceinline__ uint32_t p1(uint64_t w) const { return bq[2 * w + 1]; }
-    __device__ __forceinline__ uint32_t x(uint64_t w) const { return bx[w]; }
-};
-
 // symbol code ("-ACGNT" index) of query base q
 __device__ __forceinline__ uint32_t base_code(const uint32_t *bq, const uint32_t *bx, uint64_t q) {
     const uint64_t w = q >> 5;
     const uint32_t sh = (uint32_t)(q & 31);
-    const uint32_t p0 = (bq[2 * w] >> sh) & 1u, p1 = (bq[2 * w + 1] >> sh) & 1u, x = (bx[w] >> sh) & 1u;
-    return x ? (p0 ? 0u : 4u) : ((p1 << 1 | p0) == 3u ? 5u : (p1 << 1 | p0) + 1u);
+    return sym_code((bq[2 * w] >> sh) & 1u, (bq[2 * w + 1] >> sh) & 1u, (bx[w] >> sh) & 1u);
 }
 
 // ======================================================================= insertion layout
@@ -901,8 +891,7 @@ __device__ __forceinline__ uint64_t ev_key(const uint2 *bql, gptr_u32 xl, uint32
     uint64_t key = (uint64_t)pos | ((uint64_t)take << 11);
     for (uint32_t c = 0; c < take; c++) {
         const uint32_t b0 = (uint32_t)(p0 >> (sh + c)) & 1u, b1 = (uint32_t)(p1 >> (sh + c)) & 1u;
-        const uint32_t code = ((px >> (sh + c)) & 1u) ? (b0 ? 0u : 4u) : ((b1 << 1 | b0) == 3u ? 5u : (b1 << 1 | b0) + 1u);
-        key |= (uint64_t)code << (16 + 3 * c);
+        key |= (uint64_t)sym_code(b0, b1, (uint32_t)(px >> (sh + c)) & 1u) << (16 + 3 * c);
     }
     return key;
 }
@@ -1668,7 +1657,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(NWP <= 16 ? 
             const uint32_t e = d.lp[T.lp0 + e0 + j];
             if (lpieces) {
                 const uint4 P = ((const uint4 *)d.pc)[e];
-                walk_piece(TileMem{d.ops, d.bq, d.bx}, P, d.pc[4 * (size_t)e + 6], d.maxdel_active != 0, d.maxdel,
+                walk_piece(GlobalMem{d.ops, d.bq, d.bx}, P, d.pc[4 * (size_t)e + 6], d.maxdel_active != 0, d.maxdel,
                            [&](uint32_t, uint32_t gp, uint32_t l, uint32_t kind, uint64_t q) {
                                if (kind != S2C_RUN_EMPTY) one_run(gp, l, kind, q);
                            },

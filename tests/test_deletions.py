@@ -598,6 +598,48 @@ def test_format_guards():
     assert got == b"\xEE" * len(got)
 
 
+IMAGE = 24 * 1024 - 16   # bytes of a step's lines that still leave through the LDS image
+
+
+class SwitchScene(DelScene):
+    """One tile whose 80 events are one step of k_dels_write: lines of 307 bytes (a name of 290
+    characters, starts and ends of two digits, a coverage of three), IMAGE bytes in all: the last
+    step that leaves through the LDS image.  With over = 1 the last event's reads have two digits:
+    one byte more, the first step that goes out byte by byte."""
+
+    def __init__(self, over):
+        self.events = {(g, 1): (1, 0) for g in range(80)}
+        if over:
+            self.events[(79, 1)] = (10, 0)
+        self.skipped = {}
+        self.names = [b"N" * 290]
+        self.tile_ref = [0]
+        self.blocks = np.array([(0, TW, 10)], dtype=np.int64)
+        self.counts = np.zeros((6, PAD_L), dtype=np.uint32)
+        self.counts[:, :80] = 20
+        self.wtile = np.full(PAD_L // 32, 0xFFFFFFFF, dtype=np.uint32)
+        self.wtile[:TW // 32] = 0
+        rows = [(g, ln, n, d) for (g, ln), (n, d) in self.events.items()]
+        self.n_slots = 256
+        self.slots = np.zeros((self.n_slots, 4), dtype=np.uint32)
+        self.slots[np.random.RandomState(11).permutation(self.n_slots)[:len(rows)]] = np.array(rows, dtype=np.uint32)
+        self.n_rows = len(rows)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("over", [0, 1])
+def test_format_at_the_image_switch(over):
+    """A step of exactly the image's capacity and one of a byte more, dst shifted by 0 and by 15
+    (the image then ends at its last byte): the same text either way, the guard bytes untouched."""
+    sc = SwitchScene(over)
+    want = sc.want()
+    assert len(want) == 1 and want[0].count(b"\n") == 80 and len(want[0]) == IMAGE + over
+    assert want[0].startswith(b"N" * 290 + b"\t10\t10\t1\t1\t0\t120\n")
+    assert want[0].endswith(b"N\t89\t89\t1\t%d\t0\t120\n" % (10 if over else 1))
+    text = check_format(sc)
+    assert text == want[0] and check_format(sc, shift=15) == text
+
+
 @pytest.mark.gpu
 def test_collect_guards_and_the_overflow_word():
     """s2c_dels_collect on a real batch with tables of its own: two slots for four distinct events
