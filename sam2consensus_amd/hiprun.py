@@ -138,6 +138,10 @@ class Session:
         if n > self.dcap:
             self.hip.free(self.dbuf)
             self.dbuf, self.dcap = self.hip.malloc(n), n
+        self._grow_host(n)
+
+    def _grow_host(self, n):
+        """The pinned staging buffer alone (the fetch: the bodies need no room in the batch's)."""
         if n > self.hcap:
             self.hip.host_free(self.hbuf)
             self.hbuf, self.hcap = self.hip.host_malloc(n), n
@@ -156,6 +160,9 @@ class Session:
         engine.Workspace.fetch returns them; ``bodies`` a read-only view valid until close()."""
         t = timings if timings is not None else {}
         hip = self.hip
+        # HIP's current device belongs to the calling thread: reserve() set it on the warm-up
+        # thread only (cli._warm_session); every allocation and launch below is this thread's
+        hip.set_device(self.device)
         fill = bytes(fill)
         t0 = time.perf_counter()
         hb.ensure_layers(len(fill) != 1)   # (engine.needs_dense_layers: a fill of length != 1)
@@ -213,6 +220,7 @@ class Session:
         """engine.Workspace.fetch_device + to_host: statistics and body lengths to the host, the
         bodies compacted on the device (s2c_gather_bodies_dev) and copied out once."""
         hip = self.hip
+        hip.set_device(self.device)   # (as run(): the calling thread's device)
         R, nb = i.n_refs, i.n_tiles
         stats = np.zeros((R, T, 4), dtype=np.uint64)
         if T * nb == 0:
@@ -241,7 +249,7 @@ class Session:
             L.check(lib.s2c_gather_bodies_dev(C.c_void_p(bufs["out"]), cap, C.c_void_p(abuf + aoffs[0]),
                                               C.c_void_p(abuf + aoffs[1]), T * nb, C.c_void_p(abuf + aoffs[2]),
                                               C.c_void_p()))
-            self._grow(total)
+            self._grow_host(total)   # (the device batch buffer stays: only the host side takes the bodies)
             hip.memcpy(self.hbuf, abuf + aoffs[2], total, _D2H)   # (synchronous: the null stream's work is done)
         finally:
             hip.free(abuf)

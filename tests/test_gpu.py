@@ -489,7 +489,8 @@ def test_unsorted_accumulation_on_device_configs(tmp_path, name, over, args):
     assert got == want
 
 
-@pytest.mark.parametrize("name,over,thr,md,fill", [
+# (name, overrides, thresholds, min depth, fill): also run through hiprun.Session (test_cli_path.py)
+PIPELINE_CASES = [
     ("c2", {"n_refs": 6}, [0.25, 0.5, 0.75], 1, b"-"),
     # long insertions: > 1024 insertion columns in a tile → the HBM column path
     ("c2", {"n_refs": 2, "depth": 60.0, "ins_frac": 0.6, "ins_max": 60}, [0.1, 0.5], 1, b"-"),
@@ -509,7 +510,10 @@ def test_unsorted_accumulation_on_device_configs(tmp_path, name, over, args):
     ("c2", {"n_refs": 4, "depth": 3.0}, [0.2, 0.4, 0.6, 0.8, 1.0], 1, b"N"),
     # many '-'/'N' entries per work item (> 1024: past the register prefetch, from HBM)
     ("c2", {"n_refs": 2, "del_frac": 0.6, "del_max": 8, "n_rate": 0.05}, [0.25, 0.5], 1, b"-"),
-])
+]
+
+
+@pytest.mark.parametrize("name,over,thr,md,fill", PIPELINE_CASES)
 def test_device_pipeline_equals_batch_model(name, over, thr, md, fill):
     """stats / block offsets / bytes of the HIP stages == the batch model (tests/batch_model.py)."""
     from sam2consensus_amd import configs
