@@ -372,21 +372,12 @@ def consensus_batch_hip(sess, hb, thresholds, prefix, min_depth=1, fill=b"-", nc
     return files
 
 
-def _consensus_files_tables(filename, thresholds, prefix, min_depth, fill, nchar, maxdel_active, device, log, req,
-                            deletions=None):
-    """consensus_files with the tables of ``req`` (table.request) and the deletion table: the
-    torch engine path (consensus_batch)."""
-    import torch
-
-    from . import _lib
+def _parse_file(filename, maxdel_active, log, timings, t0):
+    """The read pass over one file → its HostBatch; ``timings["parse"]``: the seconds since ``t0``,
+    the run's start.  A reference error is logged as the reference would have (``_log_failed_parse``)
+    and raised; the summary of a clean pass is the caller's to log."""
     from .batch import Parser
 
-    t = {}
-    t0 = time.perf_counter()
-    dev = torch.device(device if device is not None else "cuda:%d" % int(os.environ.get("LOCAL_RANK", "0")))
-    if dev.type != "cuda" or not torch.cuda.is_available():
-        raise RuntimeError("sam2consensus_amd needs a ROCm GPU (torch.cuda unavailable); no CPU fallback")
-    _lib.plan_for_device(dev)   # (the plan's grid shaping, before the parse builds it)
     p = Parser(maxdel_active, 150)
     try:
         p.feed_file(filename)
@@ -397,7 +388,22 @@ def _consensus_files_tables(filename, thresholds, prefix, min_depth, fill, nchar
         raise
     finally:
         p.close()
-    t["parse"] = time.perf_counter() - t0
+    timings["parse"] = time.perf_counter() - t0
+    return hb
+
+
+def _consensus_files_tables(filename, thresholds, prefix, min_depth, fill, nchar, maxdel_active, device, log, req,
+                            deletions=None):
+    """consensus_files with the tables of ``req`` (table.request) and the deletion table: the
+    torch engine path (consensus_batch)."""
+    from . import _lib
+    from .engine import _dev
+
+    t = {}
+    t0 = time.perf_counter()
+    dev = _dev(device)
+    _lib.plan_for_device(dev)   # (the plan's grid shaping, before the parse builds it)
+    hb = _parse_file(filename, maxdel_active, log, t, t0)
     if log:
         _log_summary(log, hb.info)
     files = consensus_batch(hb, thresholds, prefix, min_depth, fill, nchar, dev, t, deletions=deletions, **req)
@@ -416,7 +422,6 @@ def consensus_files(filename, thresholds, prefix, min_depth=1, fill=b"-", nchar=
     if req or (deletions is not None and deletions is not False):
         return _consensus_files_tables(filename, thresholds, prefix, min_depth, fill, nchar, maxdel_active, device, log, req,
                                        deletions)
-    from .batch import Parser
     from .hiprun import Session, device_index
 
     t = {}
@@ -424,17 +429,7 @@ def consensus_files(filename, thresholds, prefix, min_depth=1, fill=b"-", nchar=
     sess = Session(device_index(device))
     warm = _warm_session(sess, upload_estimate(filename), t)   # (the device comes up while the host parses)
     try:
-        p = Parser(maxdel_active, 150)
-        try:
-            p.feed_file(filename)
-            hb = p.finish()
-        except REF_ERRORS:
-            if log:
-                _log_failed_parse(log, p)
-            raise
-        finally:
-            p.close()
-        t["parse"] = time.perf_counter() - t0
+        hb = _parse_file(filename, maxdel_active, log, t, t0)
         _join_session(sess, warm)
         if log:
             _log_summary(log, hb.info)
@@ -466,7 +461,7 @@ def run_text(sam_text, argv, device=None, deletions=None, **tables):
         hb = parse_text(sam_text, not isinstance(args.maxdel, str), 150)
         files = consensus_batch(hb, thresholds, os.fsencode(prefix), args.min_depth,
                                 os.fsencode(args.fill), args.n, device, deletions=dels, **req)
-    except (KeyError, IndexError, ValueError, ZeroDivisionError, OverflowError) as e:
+    except REF_ERRORS as e:
         return type(e).__name__, {}
     return "ok", {k.decode("latin-1"): v.decode("latin-1") for k, v in files.items()}
 

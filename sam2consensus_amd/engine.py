@@ -7,7 +7,6 @@ fallback: without a visible GPU ``DeviceBatch`` raises.
 from __future__ import annotations
 
 import ctypes as C
-import os
 import time
 
 import numpy as np
@@ -15,28 +14,27 @@ import torch
 
 from . import _lib as L
 from ._lib import lib
-from .devargs import EXT_ARRAYS, LEAN_ARRAYS, UPLOAD, fill_dev, fill_ext, fill_lean
+from .devargs import (BUFFERS, UPLOAD, ZEROED, body_starts, device_index, empty_result, layout, needs_dense_layers,
+                      padded_end, ref_stats, run_args, upload_arrays, workspace_plan)
 from .table import DEL_KEY, TABLES
 
 
 def _dev(device):
-    if device is None:
-        device = "cuda:%d" % int(os.environ.get("LOCAL_RANK", "0"))
-    d = torch.device(device)
-    if d.type != "cuda" or not torch.cuda.is_available():
+    """``device`` (devargs.device_index's forms, or a torch.device) as a torch.device."""
+    if not torch.cuda.is_available():
         raise RuntimeError("sam2consensus_amd needs a ROCm GPU (torch.cuda unavailable); no CPU fallback")
-    return d
+    return torch.device("cuda", device_index(device))
 
 
 def _up(arr, device):
-    """numpy u32/i64 array → device tensor (bit-preserving, ≥1 element)."""
+    """numpy array → device tensor (bit-preserving, ≥ 16 bytes)."""
     a = np.ascontiguousarray(arr)
     if a.dtype == np.uint32:
         a = a.view(np.int32)
     elif a.dtype == np.uint64:
         a = a.view(np.int64)
     if a.size == 0:
-        a = np.zeros(4, dtype=a.dtype if a.dtype != np.uint8 else np.uint8)
+        a = np.zeros(max(4, 16 // a.itemsize), dtype=a.dtype)
     return torch.from_numpy(a).to(device, non_blocking=False)
 
 
@@ -54,8 +52,6 @@ class Uploader:
     kernels run.  Pageable H2D of a GB-sized batch runs at ~2 GB/s on the box; this at the
     memcpy rate."""
 
-    ALIGN = 256
-
     def __init__(self, device=None, nbuf=4, chunk=32 << 20):
         self.device = _dev(device)
         self.copy_stream = torch.cuda.Stream(self.device)
@@ -64,13 +60,6 @@ class Uploader:
         self.events = [None] * nbuf     # the copy out of each slot
         self.k = 0
         self.timing = {"alloc": 0.0, "wait": 0.0, "pack": 0.0, "issue": 0.0}   # host seconds, cumulative
-
-    def _layout(self, arrays):
-        offs, total = [], 0
-        for a in arrays:
-            offs.append(total)
-            total += (max(a.nbytes, 16) + self.ALIGN - 1) // self.ALIGN * self.ALIGN
-        return offs, max(total, self.ALIGN)
 
     def _slot(self):
         i = self.k % len(self.slots)
@@ -94,10 +83,10 @@ class Uploader:
         return self
 
     def upload(self, arrays):
-        """numpy arrays → device uint8 views (each 256-byte aligned, ≥ 16 bytes, zero-padded
-        to its 16-byte end), in HBM once the compute stream reaches this point."""
-        arrays = [np.ascontiguousarray(a).reshape(-1).view(np.uint8) for a in arrays]
-        offs, total = self._layout(arrays)
+        """Flat uint8 arrays (devargs.upload_arrays) → device uint8 views (devargs.layout: each
+        256-byte aligned, ≥ 16 bytes, zero-padded to its 16-byte end), in HBM once the compute
+        stream reaches this point."""
+        offs, total = layout([a.nbytes for a in arrays])
         compute = torch.cuda.current_stream(self.device)
         t0 = time.perf_counter()
         # the allocation on the copy stream (free there in its order: no wait for the compute
@@ -105,7 +94,7 @@ class Uploader:
         with torch.cuda.stream(self.copy_stream):
             dev = torch.empty(total, dtype=torch.uint8, device=self.device)
         self.timing["alloc"] += time.perf_counter() - t0
-        ends = [o + (max(a.nbytes, 16) + 15) // 16 * 16 for a, o in zip(arrays, offs)]   # (zero pad to 16 bytes)
+        ends = [padded_end(o, a.nbytes) for a, o in zip(arrays, offs)]   # (zero pad to 16 bytes)
         ai = 0
         ev = None
         for w0 in range(0, max(ends) if ends else 0, self.chunk):
@@ -177,13 +166,6 @@ def default_uploader(device=None):
     return _UPLOADERS[d]
 
 
-def needs_dense_layers(fill=b"-", counts=False):
-    """Whether a Workspace runs the dense tiles through k_tile (so its DeviceBatch needs
-    ``dense_layers=True``): the counts-only modes, and a fill of length != 1 (k_tile_dense
-    emits one char per position)."""
-    return bool(counts) or len(fill.encode("latin-1") if isinstance(fill, str) else bytes(fill)) != 1
-
-
 class DeviceBatch:
     """The packed batch resident in HBM (inputs of every launch).  With an ``Uploader`` (by
     default for batches of 64 MB or more) the arrays go through its pinned staging ring and
@@ -197,8 +179,7 @@ class DeviceBatch:
         # them through k_tile); the pileup reads them in place, so by default they are not built
         self.hb = hb.ensure_layers(dense_layers)
         self.info = type(hb.info).from_buffer_copy(hb.info)   # (the arrays as uploaded)
-        # (the per-word arrays over the batch's word span only: HostBatch.device_view)
-        arrays = [np.asarray(hb.device_view(n)).reshape(-1) for n in self.ARRAYS]
+        arrays = upload_arrays(hb)
         if uploader is None and sum(a.nbytes for a in arrays) >= (64 << 20):
             uploader = default_uploader(self.device)   # (large batches: pinned chunks, not pageable copies)
         if uploader is not None:
@@ -229,72 +210,45 @@ class Workspace:
             raise ValueError("counts-only modes and a fill of length != 1 run the dense tiles through k_tile: "
                              "DeviceBatch(..., dense_layers=True)")
         self.T = len(thresholds)
-        sz = L.WsSizes()
-        L.check(lib.s2c_workspace_sizes(C.byref(i), self.T, C.byref(sz)))
-        self.sizes = sz
-        u8 = lambda n: torch.empty(max(int(n), 16), dtype=torch.uint8, device=dev)  # noqa: E731
-        z8 = lambda n: torch.zeros(max(int(n), 16), dtype=torch.uint8, device=dev)  # noqa: E731
-        self.thr = torch.tensor([float(t) for t in thresholds], dtype=torch.float64, device=dev)
         fill = bytes(fill)
         self.fill_bytes = fill
+        plan = workspace_plan(i, self.T, fill)
+        self.sizes, self.fill_w, self.out_stride = plan.ws, plan.fill_w, plan.out_stride
+        self.thr = torch.tensor([float(t) for t in thresholds], dtype=torch.float64, device=dev)
         self.fill = torch.tensor(list(fill) or [0], dtype=torch.uint8, device=dev)
-        self.runs = u8(sz.runs)
-        # insertion hash tables: zero before the first run; every run leaves them zero
-        self.ibkt, self.ilong, self.ilong_n = z8(sz.ibkt), u8(sz.ilong), z8(sz.ilong_n)
-        # counts live in HBM only for deep / general tiles (unless a test asks for all of them)
         self.keep_counts = keep_counts
-        if counts is not None:   # running totals shared by streamed batches (u8 view, 6·L u32)
-            if counts.numel() * counts.element_size() < 6 * i.padded_len * 4:
-                raise ValueError("counts buffer smaller than 6 x padded_len u32")
-            self.counts = counts
-        else:   # (zero before the first run; s2c_consensus leaves it zero: s2c_dev.counts)
-            self.counts = z8(6 * i.padded_len * 4 if keep_counts else sz.counts)
         self._counts_filled = False   # s2c_pileup_counts leaves counts filled: zeroed before a run
         self._tables_held = False     # the batch's insertion tables are in ibkt / ilong (accumulate(keep_tables=True))
-        self.ins_cols = u8(sz.ins_cols)
-        self.ins_chr = u8(sz.ins_chr)
-        self.blk_len = u8(sz.blk_len)
-        self.tile_stats = u8(sz.tile_stats)
-        # body slots: per threshold max(1, len(fill)) bytes per padded position + the columns
-        self.fill_w = max(1, len(fill))
-        self.out_stride = self.fill_w * i.padded_len + i.n_cols
-        cap = int(sz.out_per_fill) * self.fill_w + int(sz.out_fixed)
-        self.out = u8(cap)
-        # the maxdel rule (:210) runs on the device: the parser's setting unless overridden
-        if maxdel_active is None:
-            maxdel_active = getattr(db.hb, "maxdel_active", True)
-        if maxdel is None:
-            maxdel = getattr(db.hb, "maxdel", 150)
-        bufs = {n: getattr(self, n).data_ptr() for n in ("runs", "ibkt", "ilong", "ilong_n", "counts", "ins_cols",
-                                                           "ins_chr", "tile_stats", "blk_len", "out")}
+        if counts is not None and counts.numel() * counts.element_size() < 6 * i.padded_len * 4:
+            raise ValueError("counts buffer smaller than 6 x padded_len u32")
+        for n in BUFFERS:   # one tensor per buffer, devargs.ZEROED zero before the first run
+            size = plan.sizes[n]
+            if n == "counts":
+                # counts live in HBM only for deep / general tiles, unless a test asks for all of
+                # them or streamed batches share their running totals (u8 view, 6·L u32)
+                if counts is not None:
+                    self.counts = counts
+                    continue
+                if keep_counts:
+                    size = 6 * i.padded_len * 4
+            setattr(self, n, (torch.zeros if n in ZEROED else torch.empty)(max(size, 16), dtype=torch.uint8, device=dev))
+        bufs = {n: getattr(self, n).data_ptr() for n in BUFFERS}
         bufs.update(thresholds=self.thr.data_ptr(), fill=self.fill.data_ptr())
-        d = fill_dev(i, {name: getattr(db, name).data_ptr() for name in DeviceBatch.ARRAYS}, bufs, self.T, min_depth,
-                     fill, maxdel_active, maxdel, cap)
-        if tile_range is not None:
+        self.dev, self.ext, self.lean = run_args(db.hb, i, {n: getattr(db, n).data_ptr() for n in UPLOAD}, bufs, self.T,
+                                                 min_depth, fill, plan.out_cap, maxdel_active, maxdel)
+        if tile_range is not None:   # the work lists and the dense windows' rows of [t0, t1) in place of the batch's
             t0, t1 = tile_range
             hb = db.hb
-            keep = lambda a, col: a[(a[:, col] >= t0) & (a[:, col] < t1)] if len(a) else a  # noqa: E731
-            self._sel = {"items": keep(hb.items, 0), "dense": keep(hb.dense, 0), "dwin": keep(hb.dwin, 0),
-                         "deep": hb.deep[(hb.deep >= t0) & (hb.deep < t1)]}
-            for name, a in self._sel.items():
-                t = _up(np.ascontiguousarray(a).reshape(-1), dev)
-                self._sel[name] = t
-                setattr(d, name, _ptr(t))
-            d.n_items = int(len(keep(hb.items, 0)))
-            d.n_dense = int(len(keep(hb.dense, 0)))
-            d.n_deep = int(((hb.deep >= t0) & (hb.deep < t1)).sum())
-        self.dev = d
-        # the dense windows' extension and its lean part (s2c_run_lean / s2c_pileup_lean): their rows
-        # filtered like dwin
-        self.ext = fill_ext(db.hb, {name: getattr(db, name).data_ptr() for name in EXT_ARRAYS})
-        if tile_range is not None:
-            sel = (db.hb.dwin[:, 0] >= t0) & (db.hb.dwin[:, 0] < t1) if len(db.hb.dwin) else np.zeros(0, dtype=bool)
-            self._sel["dext"] = _up(np.ascontiguousarray(db.hb.dext[sel]).reshape(-1), dev)
-            self.ext.dext, self.ext.n_dext = _ptr(self._sel["dext"]), int(sel.sum())
-        self.lean = fill_lean(db.hb, {name: getattr(db, name).data_ptr() for name in LEAN_ARRAYS})
-        if tile_range is not None:
-            self._sel["drow"] = _up(np.ascontiguousarray(db.hb.drow[sel]).reshape(-1), dev)
-            self.lean.row, self.lean.n_row = _ptr(self._sel["drow"]), int(sel.sum())
+            keep = lambda a: a[(a[:, 0] >= t0) & (a[:, 0] < t1)] if len(a) else a  # noqa: E731
+            win = (hb.dwin[:, 0] >= t0) & (hb.dwin[:, 0] < t1) if len(hb.dwin) else np.zeros(0, dtype=bool)
+            sel = {"items": keep(hb.items), "dense": keep(hb.dense), "dwin": keep(hb.dwin),
+                   "deep": hb.deep[(hb.deep >= t0) & (hb.deep < t1)], "dext": hb.dext[win], "drow": hb.drow[win]}
+            self._sel = {name: _up(np.ascontiguousarray(a).reshape(-1), dev) for name, a in sel.items()}
+            d = self.dev
+            d.items, d.dense, d.dwin, d.deep = (_ptr(self._sel[n]) for n in ("items", "dense", "dwin", "deep"))
+            d.n_items, d.n_dense, d.n_deep = len(sel["items"]), len(sel["dense"]), len(sel["deep"])
+            self.ext.dext, self.lean.row = _ptr(self._sel["dext"]), _ptr(self._sel["drow"])
+            self.ext.n_dext = self.lean.n_row = int(win.sum())
 
     def stream_handle(self):
         return C.c_void_p(torch.cuda.current_stream(self.db.device).cuda_stream)
@@ -718,48 +672,31 @@ class Workspace:
         stats, offs, body = self.fetch_device()
         return stats, offs, to_host(body)
 
-    def _body_starts(self):
-        """Device int64 [T·tiles]: each fetched (threshold, tile) body's slot in ``out``,
-        t·(F·padded_len + n_cols) + F·a + cb0 (s2c.h s2c_dev.out), in [t][tile] order."""
-        if getattr(self, "_starts", None) is None:
-            nb = self.db.info.n_tiles
-            t0, t1 = self.tile_range if self.tile_range is not None else (0, nb)
-            blocks = self.db.hb.tiles[t0:t1].astype(np.int64)
-            slot = self.fill_w * blocks[:, 0] + blocks[:, 8]                     # F·a + cb0
-            starts = (np.arange(self.T, dtype=np.int64)[:, None] * self.out_stride + slot[None, :]).reshape(-1)
-            self._starts = _up(starts, self.db.device)
-        return self._starts
-
     def fetch_device(self):
         """Results with the FASTA bodies left on the device: (stats[R,T,4] u64, offs[T*nb+1]
         u64, body) — ``body`` a device uint8 tensor of exactly offs[-1] bytes, the fetched
         tiles' bodies compacted in [t][tile] order by ``s2c_gather_bodies_dev`` (only the
         statistics and the body lengths cross to the host here).  The current stream must
-        have the kernels' results (``fetch`` arranges that).
-
-        stats[r, t] = Σ over reference r's tiles of the device's per-tile statistics
-        (tiles never straddle a reference; :352-397 sums)."""
+        have the kernels' results (``fetch`` arranges that).  stats: devargs.ref_stats."""
         i = self.db.info
         dev = self.db.device
-        R, T, nb = i.n_refs, self.T, i.n_tiles
+        T, nb, tiles = self.T, i.n_tiles, self.db.hb.tiles
         t0, t1 = self.tile_range if self.tile_range is not None else (0, nb)
-        stats = np.zeros((R, T, 4), dtype=np.uint64)
-        if t1 > t0:
-            ts = self.tile_stats[: T * nb * 32].view(torch.int64).cpu().numpy().view(np.uint64).reshape(T, nb, 4)
-            ref = self.db.hb.tiles[t0:t1, 2].astype(np.int64)
-            for t in range(T):
-                np.add.at(stats[:, t, :], ref, ts[t, t0:t1])
         nr = t1 - t0
         if T * nr == 0:
-            return stats, np.zeros(1, dtype=np.uint64), torch.empty(0, dtype=torch.uint8, device=dev)
+            return empty_result(i.n_refs, T) + (torch.empty(0, dtype=torch.uint8, device=dev),)
+        ts = self.tile_stats[: T * nb * 32].view(torch.int64).cpu().numpy().view(np.uint64).reshape(T, nb, 4)
+        stats = ref_stats(ts, tiles, i.n_refs, t0, t1)
         # each tile wrote its body into its slot; a reference's body is its tiles' pieces in
-        # order: the slots compacted into [t][tile] order on the device
+        # order: the slots (devargs.body_starts, uploaded once) compacted into [t][tile] order on the device
         lens = self.blk_len[: T * nb * 8].view(torch.int64).view(T, nb)[:, t0:t1].reshape(-1)
         offs_d = torch.zeros(T * nr + 1, dtype=torch.int64, device=dev)
         torch.cumsum(lens, 0, out=offs_d[1:])
         offs = offs_d.cpu().numpy()
         total = int(offs[-1])
         body = torch.empty(max(total, 16), dtype=torch.uint8, device=dev)
-        L.check(lib.s2c_gather_bodies_dev(_ptr(self.out), self.out.numel(), _ptr(self._body_starts()), _ptr(offs_d),
+        if getattr(self, "_starts", None) is None:
+            self._starts = _up(body_starts(tiles, T, self.fill_w, self.out_stride, t0, t1), dev)
+        L.check(lib.s2c_gather_bodies_dev(_ptr(self.out), self.out.numel(), _ptr(self._starts), _ptr(offs_d),
                                           T * nr, _ptr(body), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
         return stats, offs.astype(np.uint64), body[:total]

@@ -8,23 +8,25 @@ and fetches here: one device buffer for the packed batch and one for the workspa
 (hipMalloc, reserved on the warm-up thread while the host parses), one pinned staging
 buffer (hipHostMalloc) that the batch is packed into on the host threads and copied from in
 one DMA, the run on the null stream, and the results back through the same staging buffer.
-The kernels, their arguments (devargs.fill_dev) and the result layout are engine.Workspace's;
-the library paths that need streams, graphs or collectives (streamed batches, shards, the
-bench) keep engine.py.  No CPU fallback: without a GPU the runtime calls fail loudly.
+What is uploaded and where it lies, the workspace's buffers and sizes, the kernels' arguments
+and the fetch arithmetic are devargs.py's, shared with engine.py; this module holds the
+runtime binding (Hip), the session's buffer lifetimes and the order of its copies, memsets,
+launch, gather and timings.  The library paths that need streams, graphs or collectives
+(streamed batches, shards, the bench) keep engine.py.  No CPU fallback: without a GPU the
+runtime calls fail loudly.
 """
 from __future__ import annotations
 
 import ctypes as C
-import os
 import time
 
 import numpy as np
 
 from . import _lib as L
 from ._lib import lib
-from .devargs import BUFFERS, EXT_ARRAYS, LEAN_ARRAYS, UPLOAD, fill_dev, fill_ext, fill_lean
+from .devargs import (ALIGN, UPLOAD, ZEROED, body_starts, device_index, empty_result, layout,  # noqa: F401 - device_index: cli's import
+                      needs_dense_layers, padded_end, ref_stats, run_args, upload_arrays, workspace_plan)
 
-ALIGN = 256
 _H2D, _D2H = 1, 2                       # hipMemcpyHostToDevice, hipMemcpyDeviceToHost
 _ATTR_CUS = 63                          # hipDeviceAttributeMultiprocessorCount (ROCm 7 hip_runtime_api.h)
 
@@ -97,14 +99,6 @@ class Hip:
             self.h.hipHostFree(C.c_void_p(p))
 
 
-def _layout(sizes):
-    offs, total = [], 0
-    for n in sizes:
-        offs.append(total)
-        total += (max(int(n), 16) + ALIGN - 1) // ALIGN * ALIGN
-    return offs, max(total, ALIGN)
-
-
 class Session:
     """One device and its buffers for a one-batch run: `reserve` (the warm-up thread, while
     the host parses) makes the runtime, the plan's CU count and buffers of an estimated size
@@ -156,8 +150,8 @@ class Session:
         return np.ctypeslib.as_array((C.c_uint8 * max(int(n), 1)).from_address(self.hbuf))
 
     def run(self, hb, thresholds, min_depth=1, fill=b"-", timings=None):
-        """The batch's one run (s2c_run) → (stats[R,T,4] u64, offs[T·tiles+1] u64, bodies) as
-        engine.Workspace.fetch returns them; ``bodies`` a read-only view valid until close()."""
+        """The batch's one run (s2c_run_lean) → (stats[R,T,4] u64, offs[T·tiles+1] u64, bodies);
+        ``bodies`` a read-only view valid until close()."""
         t = timings if timings is not None else {}
         hip = self.hip
         # HIP's current device belongs to the calling thread: reserve() set it on the warm-up
@@ -165,88 +159,71 @@ class Session:
         hip.set_device(self.device)
         fill = bytes(fill)
         t0 = time.perf_counter()
-        hb.ensure_layers(len(fill) != 1)   # (engine.needs_dense_layers: a fill of length != 1)
+        hb.ensure_layers(needs_dense_layers(fill))
         i = type(hb.info).from_buffer_copy(hb.info)
-        arrays = [np.ascontiguousarray(np.asarray(hb.device_view(n)).reshape(-1)).view(np.uint8) for n in UPLOAD]
-        offs, total = _layout([a.nbytes for a in arrays])
+        arrays = upload_arrays(hb)
+        offs, total = layout([a.nbytes for a in arrays])
         self._grow(total)
         host = self._staging(total)
         for a, o in zip(arrays, offs):   # packed on the host threads (s2c_copy_bytes), 16-byte zero pads
             n = a.nbytes
             if n:
                 L.check(lib.s2c_copy_bytes(self.hbuf + o, a.ctypes.data, n))
-            end = o + (max(n, 16) + 15) // 16 * 16
-            host[o + n:end] = 0
+            host[o + n:padded_end(o, n)] = 0
         t1 = time.perf_counter()
         hip.memcpy(self.dbuf, self.hbuf, total, _H2D)
         t2 = time.perf_counter()
-        # the workspace in one allocation (its zeroed buffers: the insertion tables and counts)
+        # the workspace in one allocation
         T = len(thresholds)
-        sz = L.WsSizes()
-        L.check(lib.s2c_workspace_sizes(C.byref(i), T, C.byref(sz)))
-        fill_w = max(1, len(fill))
-        cap = int(sz.out_per_fill) * fill_w + int(sz.out_fixed)
-        wsz = {n: int(getattr(sz, n)) for n in BUFFERS if n != "out"}
-        wsz["out"] = cap
-        wsz["thresholds"], wsz["fill"] = 8 * T, max(len(fill), 1)
-        names = list(wsz)
-        woffs, wtotal = _layout([wsz[n] for n in names])
+        plan = workspace_plan(i, T, fill)
+        names = list(plan.sizes)
+        woffs, wtotal = layout([plan.sizes[n] for n in names])
         wbuf = hip.malloc(wtotal)
         try:
             bufs = {n: wbuf + o for n, o in zip(names, woffs)}
-            for n in ("ibkt", "ilong_n", "counts"):   # zero before the first run (s2c_dev)
-                hip.memset(bufs[n], max(wsz[n], 16))
+            for n in ZEROED:
+                hip.memset(bufs[n], max(plan.sizes[n], 16))
             thr = np.array([float(x) for x in thresholds], dtype=np.float64)
             fb = np.frombuffer(fill or b"\0", dtype=np.uint8)
             hip.memcpy(bufs["thresholds"], thr.ctypes.data, thr.nbytes, _H2D)
             hip.memcpy(bufs["fill"], fb.ctypes.data, fb.nbytes, _H2D)
             addr = {n: self.dbuf + o for n, o in zip(UPLOAD, offs)}
-            d = fill_dev(i, addr, bufs, T, min_depth, fill,
-                         getattr(hb, "maxdel_active", True), getattr(hb, "maxdel", 150), cap)
-            x = fill_ext(hb, {n: addr[n] for n in EXT_ARRAYS})
-            y = fill_lean(hb, {n: addr[n] for n in LEAN_ARRAYS})
+            d, x, y = run_args(hb, i, addr, bufs, T, min_depth, fill, plan.out_cap)
             t3 = time.perf_counter()
             L.check(lib.s2c_run_lean(C.byref(d), C.byref(x), C.byref(y), C.c_void_p()))
             hip.sync()
             t4 = time.perf_counter()
-            res = self._fetch(hb, i, T, fill_w, cap, bufs)
+            res = self._fetch(hb, i, T, plan, bufs)
         finally:
             hip.free(wbuf)
         t.update(h2d_pack=t1 - t0, h2d_copy=t2 - t1, workspace=t3 - t2, device_run=t4 - t3,
                  fetch=time.perf_counter() - t4)
         return res
 
-    def _fetch(self, hb, i, T, fill_w, cap, bufs):
-        """engine.Workspace.fetch_device + to_host: statistics and body lengths to the host, the
-        bodies compacted on the device (s2c_gather_bodies_dev) and copied out once."""
+    def _fetch(self, hb, i, T, plan, bufs):
+        """Statistics and body lengths to the host, the bodies compacted on the device
+        (s2c_gather_bodies_dev) and copied out once."""
         hip = self.hip
         hip.set_device(self.device)   # (as run(): the calling thread's device)
-        R, nb = i.n_refs, i.n_tiles
-        stats = np.zeros((R, T, 4), dtype=np.uint64)
+        nb = i.n_tiles
         if T * nb == 0:
-            return stats, np.zeros(1, dtype=np.uint64), b""
+            return empty_result(i.n_refs, T) + (b"",)
         ts = np.empty(T * nb * 4, dtype=np.uint64)
         hip.memcpy(ts.ctypes.data, bufs["tile_stats"], ts.nbytes, _D2H)
-        ts = ts.reshape(T, nb, 4)
-        ref = hb.tiles[:, 2].astype(np.int64)
-        for t in range(T):
-            np.add.at(stats[:, t, :], ref, ts[t])
+        stats = ref_stats(ts.reshape(T, nb, 4), hb.tiles, i.n_refs, 0, nb)
         lens = np.empty(T * nb, dtype=np.int64)
         hip.memcpy(lens.ctypes.data, bufs["blk_len"], lens.nbytes, _D2H)
         offs = np.zeros(T * nb + 1, dtype=np.int64)
         np.cumsum(lens, out=offs[1:])
         total = int(offs[-1])
-        blocks = hb.tiles.astype(np.int64)
-        out_stride = fill_w * i.padded_len + i.n_cols
-        starts = (np.arange(T, dtype=np.int64)[:, None] * out_stride
-                  + (fill_w * blocks[:, 0] + blocks[:, 8])[None, :]).reshape(-1)
+        starts = body_starts(hb.tiles, T, plan.fill_w, plan.out_stride, 0, nb)
         # (the slots, their offsets and the compacted bodies in one more device allocation)
-        aoffs, atotal = _layout([starts.nbytes, offs.nbytes, total])
+        aoffs, atotal = layout([starts.nbytes, offs.nbytes, total])
         abuf = hip.malloc(atotal)
         try:
             hip.memcpy(abuf + aoffs[0], starts.ctypes.data, starts.nbytes, _H2D)
             hip.memcpy(abuf + aoffs[1], offs.ctypes.data, offs.nbytes, _H2D)
-            L.check(lib.s2c_gather_bodies_dev(C.c_void_p(bufs["out"]), cap, C.c_void_p(abuf + aoffs[0]),
+            L.check(lib.s2c_gather_bodies_dev(C.c_void_p(bufs["out"]), plan.out_cap, C.c_void_p(abuf + aoffs[0]),
                                               C.c_void_p(abuf + aoffs[1]), T * nb, C.c_void_p(abuf + aoffs[2]),
                                               C.c_void_p()))
             self._grow_host(total)   # (the device batch buffer stays: only the host side takes the bodies)
@@ -258,14 +235,3 @@ class Session:
         body = memoryview(self._staging(total)[:total]).toreadonly() if total else memoryview(b"")
         return stats, offs.astype(np.uint64), body
 
-
-def device_index(device=None):
-    """The CLI's device: ``cuda:N`` / N / LOCAL_RANK (as engine._dev), as an index."""
-    if device is None:
-        return int(os.environ.get("LOCAL_RANK", "0"))
-    if isinstance(device, int):
-        return device
-    s = str(device)
-    if s.startswith("cuda"):
-        return int(s.split(":")[1]) if ":" in s else 0
-    raise RuntimeError("sam2consensus_amd needs a ROCm GPU device, not %r; no CPU fallback" % (device,))

@@ -1,10 +1,11 @@
 """hiprun.Session: the torch-free host path `sam2consensus.py -i ... -o ...` runs for a whole file
-on one GPU.  It shares the kernels and devargs.fill_dev / fill_ext / fill_lean with
-engine.Workspace and has its own copy of everything around them: the upload layout (one device
-allocation, 256-byte slots, 16-byte zero pads written into a reused pinned buffer), the workspace
-(one allocation, three buffers zeroed by hand), the output capacity, the dense layers' rule, the
-per-reference sum of the statistics, the body slots' starts, the gather and the result's view of
-the pinned buffer.
+on one GPU.  It shares the kernels with engine.Workspace, and through devargs.py the run's layout:
+the uploaded arrays, their 256-byte slots and 16-byte zero pads, the workspace's buffers, sizes and
+zeroed set, the output capacity, the dense layers' rule, the argument blocks, the per-reference sum
+of the statistics and the body slots' starts.  Its own are the buffers (one device allocation for
+the batch, one for the workspace, a reused pinned buffer), the order of its copies, memsets, launch
+and gather, and the result's view of the pinned buffer.  The shared functions are also pinned
+directly (the tile ranges only the engine passes them included).
 
 Without a GPU: Session against a recording stub of the HIP runtime.  Its allocations are host
 memory filled with 0xA5, every call is logged with its thread, and an access to a freed block
@@ -525,6 +526,83 @@ def test_fetch_grows_the_pinned_buffer_only(world):
     assert world.first("hipHostMalloc", main, r["at"]) is not None and sess.hcap >= len(got[2])
     _verify(world, sess, hb, thr, got)
     sess.close()
+
+
+# ------------------------------------------------------------------ the shared layout (devargs.py), directly
+def test_body_starts_over_tile_ranges():
+    """Three thresholds and a fill of width 2 on the batch with insertion columns: the whole range
+    is t·(2·padded_len + n_cols) + 2·a + cb0 in [t][tile] order, a tile range its [t][tile] slice."""
+    hb = _batch("multi")
+    Lp, nc = int(hb.info.padded_len), int(hb.info.n_cols)
+    a, cb0 = hb.tiles[:, 0].astype(np.int64), hb.tiles[:, 8].astype(np.int64)
+    whole = devargs.body_starts(hb.tiles, 3, 2, 2 * Lp + nc, 0, 3)
+    assert whole.dtype == np.int64 and whole.shape == (9,)
+    assert whole.tolist() == [t * (2 * Lp + nc) + 2 * int(a[k]) + int(cb0[k]) for t in range(3) for k in range(3)]
+    part = devargs.body_starts(hb.tiles, 3, 2, 2 * Lp + nc, 1, 3)
+    assert part.dtype == np.int64 and part.tolist() == whole.reshape(3, 3)[:, 1:3].reshape(-1).tolist()
+    none = devargs.body_starts(hb.tiles, 3, 2, 2 * Lp + nc, 1, 1)
+    assert none.dtype == np.int64 and none.shape == (0,)
+
+
+def test_ref_stats_over_tile_ranges():
+    """Random u64 statistics: each range's sums equal a plain double loop over its tiles (modulo
+    2^64), a reference without a tile in the range stays zero, and two ranges add up to their union."""
+    hb = _batch("multi")
+    R, nb, T = int(hb.info.n_refs), int(hb.info.n_tiles), 3
+    ts = np.random.default_rng(5).integers(0, 2 ** 64, size=(T, nb, 4), dtype=np.uint64)
+    got = {}
+    for t0, t1 in ((0, 1), (1, 3), (0, 3)):
+        st = got[t0, t1] = devargs.ref_stats(ts, hb.tiles, R, t0, t1)
+        assert st.dtype == np.uint64 and st.shape == (R, T, 4)
+        want = [[[0] * 4 for _ in range(T)] for _ in range(R)]
+        for t in range(T):
+            for k in range(t0, t1):
+                for j in range(4):
+                    r = int(hb.tiles[k, 2])
+                    want[r][t][j] = (want[r][t][j] + int(ts[t, k, j])) % 2 ** 64
+        assert st.tolist() == want
+        for r in set(range(R)) - {int(v) for v in hb.tiles[t0:t1, 2]}:
+            assert not st[r].any()
+    assert ((got[0, 1] + got[1, 3]) == got[0, 3]).all() and got[0, 3].any()
+
+
+def test_layout_slots_and_pads():
+    """256-byte slots that hold each buffer up to its 16-byte pad end (at least 16 bytes), disjoint."""
+    sizes = [0, 1, 16, 17, 255, 256, 257]
+    offs, total = devargs.layout(sizes)
+    assert len(offs) == len(sizes) and devargs.ALIGN == 256
+    ends = [devargs.padded_end(o, n) for o, n in zip(offs, sizes)]
+    for o, n, e, nxt in zip(offs, sizes, ends, offs[1:] + [total]):
+        assert o % 256 == 0 and e - o == (max(n, 16) + 15) // 16 * 16 and e <= nxt
+    assert devargs.layout([]) == ([], 256)
+
+
+@pytest.mark.parametrize("fill", FILLS, ids=FILL_IDS)
+def test_workspace_plan_sizes(fill):
+    """Every buffer's size is its s2c_workspace_sizes field, but out = out_per_fill · max(1, len(fill))
+    + out_fixed; the thresholds take 8 bytes each, the fill at least one byte."""
+    hb = _batch("multi")
+    i, T, F = hb.info, 3, max(1, len(fill))
+    sz = L.WsSizes()
+    L.check(L.lib.s2c_workspace_sizes(C.byref(i), T, C.byref(sz)))
+    plan = devargs.workspace_plan(i, T, fill)
+    cap = int(sz.out_per_fill) * F + int(sz.out_fixed)
+    want = {n: int(getattr(sz, n)) for n in devargs.BUFFERS if n != "out"}
+    want.update(out=cap, thresholds=8 * T, fill=max(len(fill), 1))
+    assert plan.sizes == want
+    assert (plan.fill_w, plan.out_cap, plan.out_stride) == (F, cap, F * int(i.padded_len) + int(i.n_cols))
+    assert set(devargs.ZEROED) == {"ibkt", "ilong_n", "counts"} and set(devargs.ZEROED) < set(devargs.BUFFERS)
+
+
+def test_device_index_forms(monkeypatch):
+    monkeypatch.delenv("LOCAL_RANK", raising=False)
+    assert devargs.device_index(None) == 0
+    monkeypatch.setenv("LOCAL_RANK", "3")
+    assert devargs.device_index(None) == 3
+    assert [devargs.device_index(d) for d in (2, "cuda", "cuda:5")] == [2, 0, 5]
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        devargs.device_index("cpu")
+    assert hiprun.device_index is devargs.device_index
 
 
 # ------------------------------------------------------------------ GPU tier
